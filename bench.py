@@ -5,10 +5,16 @@ A "step" is ONE synchronous evaluation of the hot path -- NIDCost::operator()<Je
 cost + 7-gradient -- over one LiDAR-camera pair at a distinct pose (7 doubles in, 8 doubles out,
 host sync), with the cloud and image already resident in HBM.  Workload at N=1 = BASELINE.json
 configs[1]: 1 pair, 10M-point Ouster-style synthetic cloud + 1920x1080 pinhole, 256 x 256 bins.
-The K steps are issued back to back through the C ABI (nidreg_eval_batch: each evaluation completes,
-host sync included, before the next starts -- an optimiser's inner loop); the K-step block is
-repeated (--blocks, default 25) and `value` / `ms_per_step` are those of the MEDIAN block, so the
-timed window is >= 100 ms and one scheduler hiccup cannot move the number (`timing` holds min / max).
+After W warm-up steps, exactly K = --steps timed steps are issued back to back through the C ABI
+(nidreg_eval_batch: each evaluation completes, host sync included, before the next starts -- an
+optimiser's inner loop), each at its own pose; `ms_per_step` = the timed window / K, `value` = 1000 / it.
+--dump-outputs DIR writes what the last timed step returned (DIR/cost.npy, DIR/grad.npy, float64); the
+inputs (scene, poses) are seeded, so two builds can be compared output for output.
+
+A plain run does only that and prints the line.  --full adds everything else, as before: the K-step block
+repeated (--blocks, default 25; `repeated_blocks` holds the median / min / max block), the roofline and
+per-kernel event times, the other entry points, the view-culled and pipelined forms, the other BASELINE
+configs, the CPU baseline, time to solution, the strong-scaling inputs and, at N>1, the multi_gpu cases.
 
 N>1: one process per GPU.  Launched by `python -m torch.distributed.run ... bench.py --gpus N` (the
 driver's form), or plainly as `python bench.py --gpus N`, which re-launches itself that way.
@@ -20,8 +26,8 @@ driver's form), or plainly as `python bench.py --gpus N`, which re-launches itse
                         int64 fixed-point histogram (+ the 7-gradient) per evaluation -- plus the single-process
                         route of the C ABI (desc.device_ids: direct GPU-to-GPU exchange inside nidreg_eval).
 
-Prints ONE JSON line on rank 0 with `roofline` (per evaluation; per kernel; VALU issue) and, at
-N=1, `cpu_baseline` (the oracle timed on the host cores on a bounded sample).
+Prints ONE JSON line on rank 0; with --full it carries `roofline` (per evaluation, SURVEY 8d; per kernel;
+VALU issue) and, at N=1, `cpu_baseline` (the oracle timed on the host cores on a bounded sample).
 """
 import argparse
 import json
@@ -197,7 +203,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--blocks", type=int, default=25, help="repetitions of the K-step timed block (median reported)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: repeated blocks, roofline, other entry points / configs, CPU baseline, multi_gpu cases")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--blocks", type=int, default=25, help="--full: repetitions of the K-step block for `repeated_blocks` (median reported)")
     ap.add_argument("--points", type=int, default=10_000_000)
     ap.add_argument("--camera", default="pinhole_1080p")
     ap.add_argument("--bins", type=int, default=256)
@@ -212,6 +220,8 @@ def main():
     ap.add_argument("--extra-points-scale", type=float, default=1.0, help="scale the point counts of the multi_gpu.* cases (tests)")
     ap.add_argument("--single-process-leg", default=None, help=argparse.SUPPRESS)  # internal: the child process of multi_gpu.single_process_sharded
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.single_process_leg:
         if os.environ.get("NIDREG_BENCH_ONE_GPU"):
@@ -306,6 +316,30 @@ def main():
         med = float(np.median(secs))
         return {"ms_per_step": 1e3 * med / steps, "block_s": secs, "median_s": med, "distinct_poses": int(min(len(pool), steps * blocks))}
 
+    def measure_window(cost, poses, steps, warmup):
+        """The headline: W warm-up steps, then exactly `steps` timed steps at distinct poses in ONE window (barrier + device
+        sync on both sides, MAX over ranks).  The warm-up goes through the timed path.  `last` is what the last timed step
+        returned: (ok, cost, grad)."""
+        batch = hasattr(cost, "eval_batch")
+        if batch and warmup > 0:
+            ok, _, _ = cost.eval_batch(np.ascontiguousarray([poses[k % len(poses)] for k in range(warmup)]))
+            assert ok, "evaluation rejected during warm-up"
+        for k in range(0 if batch else warmup):
+            ok, c, g = cost(poses[k % len(poses)])
+            assert ok, "evaluation rejected during warm-up"
+        block = np.ascontiguousarray([poses[(warmup + k) % len(poses)] for k in range(steps)])
+        sync()
+        t0 = time.perf_counter()
+        if batch:
+            ok, cs, gs = cost.eval_batch(block)
+            last = (ok, float(cs[-1]), np.array(gs[-1]))
+        else:
+            for x in block:
+                last = cost(x)
+        sync()
+        secs = max_over_ranks([time.perf_counter() - t0])
+        return {"ms_per_step": 1e3 * secs[0] / steps, "block_s": secs, "median_s": secs[0], "distinct_poses": int(min(len(poses), steps)), "last": last}
+
     def timing_summary(m, steps):
         return {"blocks": len(m["block_s"]), "steps_per_block": steps, "window_ms": round(1e3 * sum(m["block_s"]), 2),
                 "ms_per_step_median": round(m["ms_per_step"], 5), "ms_per_step_min": round(1e3 * min(m["block_s"]) / steps, 5),
@@ -356,10 +390,24 @@ def main():
     torch.cuda.synchronize()
     t_setup = time.time() - t0
 
-    m = measure(cost, poses, args.steps, args.warmup, args.blocks)
+    m = measure_window(cost, poses, args.steps, args.warmup)
     ms_per_step = m["ms_per_step"]
     units_per_step = world if args.mode == "pairs" else 1
     value = units_per_step * 1e3 / ms_per_step
+    if args.dump_outputs and rank == 0:
+        ok_last, cost_last, grad_last = m["last"]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "cost.npy"), np.array([cost_last], dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "grad.npy"), np.asarray(grad_last, dtype=np.float64).reshape(7))
+        np.save(os.path.join(args.dump_outputs, "ok.npy"), np.array([1.0 if ok_last else 0.0], dtype=np.float64))
+    repeated = None
+    ms_steady = ms_per_step
+    if args.full:
+        # the same K-step block repeated (>= --blocks times, a window of >= 150 ms), median / min / max block; the --full figures
+        # derived from the time of one evaluation (roofline, shard_proxy, ...) use its median, which a short headline window does not pin
+        m_rep = measure(cost, poses, args.steps, 0, args.blocks)
+        repeated = timing_summary(m_rep, args.steps)
+        ms_steady = m_rep["ms_per_step"]
 
     inner = cost.inner if hasattr(cost, "inner") else cost
     plain = not hasattr(cost, "inner")
@@ -397,10 +445,11 @@ def main():
                 "ranks_seen": ranks_seen,
             },
             "timing": timing_summary(m, args.steps),
+            "repeated_blocks": repeated,
             # construction folded in at the reference's usage (one cost object per pair per outer iteration, ~50 evaluations each)
             "amortised_50_evals_per_handle": {
-                "first_handle_of_the_process": round(units_per_step * 50.0 / (t_setup + 50.0 * ms_per_step * 1e-3), 1),  # includes loading the code objects, growing the scratch arena
-                "later_handles": round(units_per_step * 50.0 / (extra["setup_again_s"] + 50.0 * ms_per_step * 1e-3), 1) if extra and "setup_again_s" in extra else None,
+                "first_handle_of_the_process": round(units_per_step * 50.0 / (t_setup + 50.0 * ms_steady * 1e-3), 1),  # includes loading the code objects, growing the scratch arena
+                "later_handles": round(units_per_step * 50.0 / (extra["setup_again_s"] + 50.0 * ms_steady * 1e-3), 1) if extra and "setup_again_s" in extra else None,
             },
             "roofline": roof,
             "pipelined": pipelined,
@@ -460,7 +509,7 @@ def main():
 
     # ---- kernel timing with HIP events on the handle's own stream (extra, untimed evaluations)
     python_call_rate = None
-    if rank == 0 and plain:
+    if rank == 0 and plain and args.full:
         t1 = time.perf_counter()
         for k in range(args.steps):
             cost(poses[k % len(poses)])
@@ -488,7 +537,7 @@ def main():
         kstats = _matching_kernel_stats(n_local, scene.width, scene.height, args.bins, args.precision, build, camera=args.camera)
         ks = {k_: v["avg_ns"] * 1e-6 for k_, v in kstats["kernels"].items()} if kstats else {}
         eval_bytes = algorithmic_bytes(n_local, scene.width, scene.height, args.bins)
-        eval_achieved = eval_bytes / (ms_per_step * 1e-3) / 1e9
+        eval_achieved = eval_bytes / (ms_steady * 1e-3) / 1e9
         dom = "k_spline_hist" if kt["hist"] >= kt["grad"] else "k_spline_grad"
         dom_ms_events = max(kt["hist"], kt["grad"])
         # algorithmic bytes ONE launch of a streaming pass moves: 16 B/point + the 8-bit image + the B x B 64-bit histogram
@@ -529,7 +578,7 @@ def main():
                 "busy_frac_while_waves_alive": alive or None,
                 "insts_per_point": {k_: round(v * 64.0 / n_local, 1) for k_, v in insts.items()},
                 "issue_floor_us": {k_: round(v, 2) for k_, v in floor_us.items()},
-                "frac_of_evaluation": round(sum(floor_us.values()) / (ms_per_step * 1e3), 3),
+                "frac_of_evaluation": round(sum(floor_us.values()) / (ms_steady * 1e3), 3),
                 "model": "SQ_INSTS_VALU x 4 clk / (1024 SIMDs x 2.4 GHz)",
                 "source": pmc["_file"],
             }
@@ -566,7 +615,7 @@ def main():
 
     # ---- the other two entry points of the path on the same resident workload (informational):
     # cost only (T = double instantiation, line-search probes) and the Nelder-Mead twin
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         def rate(fn, n=30):
             for k in range(3):
                 fn(k)
@@ -618,7 +667,7 @@ def main():
 
     # ---- the same workload with the evaluations queued ahead (nidreg_submit / nidreg_wait): what a caller with independent
     # poses in hand gets -- Nelder-Mead's initial simplex, multi-start, batches; `value` stays the synchronous rate
-    if rank == 0 and world == 1 and plain:
+    if rank == 0 and world == 1 and plain and args.full:
         bp = np.ascontiguousarray([poses[k % len(poses)] for k in range(args.steps)])
         cost.eval_batch(bp[:8], pipelined=True)
         tp = []
@@ -631,7 +680,7 @@ def main():
 
     # ---- the view-culled form of the workload (what `calibrate` evaluates: visual_camera_calibration.cpp:201-206 culls before
     # every inner solve): the scene plus a copy pushed out of the view, culled and bucketed on the device
-    if rank == 0 and world == 1 and plain and not args.no_config_legs:
+    if rank == 0 and world == 1 and plain and args.full and not args.no_config_legs:
         try:
             from direct_visual_lidar_calibration_amd import se3 as _se3c
 
@@ -648,7 +697,7 @@ def main():
                 tcs.append((time.perf_counter() - t1) / len(bp))
             kept = int(cc.info()["num_points"])
             us = 1e6 * float(np.median(tcs))
-            culled = {"in_pts": int(2 * pts.shape[0]), "kept": kept, "us_per_eval": round(us, 2), "ns_per_pt": round(1e3 * us / kept, 3), "headline_ns_per_pt": round(1e6 * ms_per_step / pts.shape[0], 3),
+            culled = {"in_pts": int(2 * pts.shape[0]), "kept": kept, "us_per_eval": round(us, 2), "ns_per_pt": round(1e3 * us / kept, 3), "headline_ns_per_pt": round(1e6 * ms_steady / pts.shape[0], 3),
                       "frac": round(algorithmic_bytes(kept, scene.width, scene.height, args.bins) / (us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4), "seg": [int(cc.info()["segmented"]), int(cc.info()["segmented_hist"])]}
             cc.close()
             cl.close()
@@ -656,7 +705,7 @@ def main():
             culled = {"error": f"{type(exc).__name__}: {exc}"[:200]}
 
     # ---- CPU baseline: the oracle (faithful restatement, 1 core, Jet<7>) on a bounded sample
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_sample > 0:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and args.cpu_sample > 0:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib  # test infrastructure, used here only as the timed CPU baseline
 
@@ -732,11 +781,11 @@ def main():
             cpu["generous_cores"] = nthr
 
     default_workload = (args.points, args.camera, args.bins) == (10_000_000, "pinhole_1080p", 256)
-    if rank == 0 and world == 1 and plain and not args.no_config_legs and (default_workload or os.environ.get("NIDREG_BENCH_FORCE_LEGS")):
+    if rank == 0 and world == 1 and plain and args.full and not args.no_config_legs and (default_workload or os.environ.get("NIDREG_BENCH_FORCE_LEGS")):
         shard_proxy = {"note": "ONE-GPU PROJECTION, NOT A MEASUREMENT: t_shard = this GPU's time on 1/8 of the cloud (index slice, the pair's fixed-point unit); "
                                "projected speed-up at 8 GPUs = t_full / (t_shard + exchange)"}
         try:
-            shard_proxy["c2"] = dict(shard_proxy_ms(proj, scene, args.bins), camera=args.camera, full_ms=round(ms_per_step, 5))
+            shard_proxy["c2"] = dict(shard_proxy_ms(proj, scene, args.bins), camera=args.camera, full_ms=round(ms_steady, 5))
         except Exception as exc:
             shard_proxy["c2"] = {"error": f"{type(exc).__name__}: {exc}"[:200]}
     cost.close()
@@ -744,7 +793,7 @@ def main():
 
     # ---- every other BASELINE.json config on this one GPU (one pair each; the sharded / per-GPU forms are the N > 1 legs):
     # ms per synchronous cost+Jacobian evaluation, algorithmic GB/s, fraction of the HBM roof
-    if rank == 0 and world == 1 and not args.no_config_legs and (default_workload or os.environ.get("NIDREG_BENCH_FORCE_LEGS")):
+    if rank == 0 and world == 1 and args.full and not args.no_config_legs and (default_workload or os.environ.get("NIDREG_BENCH_FORCE_LEGS")):
         configs = {}
         t_legs = time.time()
         for key, camera, n_points, bins_ in (("c1", "pinhole_vga", 100_000, 16), ("c3", "equirect_2k", 10_000_000, 256), ("c3b", "omnidir_2k", 10_000_000, 256),
@@ -800,7 +849,11 @@ def main():
     # and wait for each other inside kernels -- bounded there by the wall clock, here by a timeout), and the RCCL chain's floor
     if shard_proxy is not None:
         try:
-            r_ = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "shard_cost.py"), str(args.bins), "--tiny-only"], capture_output=True, text=True, timeout=120)
+            # (the child's own queue count: a GPU_MAX_HW_QUEUES inherited from the caller's environment would win over the script's default)
+            r_ = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "shard_cost.py"), str(args.bins), "--tiny-only"], capture_output=True, text=True, timeout=120,
+                                env=dict(os.environ, GPU_MAX_HW_QUEUES="24"))
+            if r_.returncode != 0 or not r_.stdout.strip():
+                raise RuntimeError(f"tools/shard_cost.py exit code {r_.returncode}: " + (r_.stderr or "").strip()[-240:])
             row = json.loads(r_.stdout.strip().splitlines()[-1])["tiny"]
             base = row["plain_three_kernels"]["us_per_eval_cost_grad"]
             shard_proxy["exchange_us_2_colocated"] = round(row["shards_2"]["us_per_eval_cost_grad"] - base, 2)
@@ -810,7 +863,7 @@ def main():
             shard_proxy["exchange_error"] = f"{type(exc).__name__}: {exc}"[:200]
         w1 = (extra or {}).get("inlib_rccl_world1", {})
         if w1.get("evals_per_s"):
-            shard_proxy["rccl_world1_overhead_us"] = round(1e6 / w1["evals_per_s"] - 1e3 * ms_per_step, 2)
+            shard_proxy["rccl_world1_overhead_us"] = round(1e6 / w1["evals_per_s"] - 1e3 * ms_steady, 2)
         proj8 = {}
         for key in ("c2", "c3", "c5"):
             e_ = shard_proxy.get(key, {})
@@ -828,7 +881,7 @@ def main():
     # ---- time to solution (north star: final T_lidar_camera within 1e-3 m / 1e-3 rad of the CPU path on identical inputs): the whole
     # `calibrate` outer loop on the GPU engine and, as a CPU-baseline leg, the same host driver on the oracle -- BASELINE configs[0]
     # (serial oracle) and configs[1] (the oracle's OpenMP split over points on every host core; bounded on both sides)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_config_legs and (default_workload or os.environ.get("NIDREG_BENCH_FORCE_LEGS")):
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not args.no_config_legs and (default_workload or os.environ.get("NIDREG_BENCH_FORCE_LEGS")):
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         tts_out = {}
         try:
@@ -844,7 +897,7 @@ def main():
             tts_out["error"] = f"{type(exc).__name__}: {exc}"[:300]
 
     # ------------------------------------------------------------------ N>1: the other multi-GPU cases, same JSON line
-    if world > 1 and not args.no_extra_legs:
+    if world > 1 and args.full and not args.no_extra_legs:
         from direct_visual_lidar_calibration_amd import parallel
 
         multi = {"ranks_seen": ranks_seen}

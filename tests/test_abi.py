@@ -34,12 +34,12 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in lib.nidreg_version()
 
 
-def test_desc_struct_layout_matches_header():
+def test_desc_struct_layout_matches_header(tmp_path):
     """sizeof(nidreg_desc) seen by the C compiler == the ctypes mirror."""
     from direct_visual_lidar_calibration_amd import _lib
 
     code = '#include <stdio.h>\n#include "nidreg.h"\nint main(){printf("%zu %zu %zu\\n", sizeof(nidreg_desc), __builtin_offsetof(nidreg_desc, image), __builtin_offsetof(nidreg_desc, ext_out));return 0;}\n'
-    exe = "/tmp/_nidreg_sizeof"
+    exe = str(tmp_path / "nidreg_sizeof")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=code.encode(), check=True)
     out = subprocess.check_output([exe]).decode().split()
     assert int(out[0]) == ctypes.sizeof(_lib.NidregDesc)

@@ -17,8 +17,11 @@ import parity
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
 CSRC = os.path.join(ROOT, "direct_visual_lidar_calibration_amd", "csrc")
-EXE = os.path.join(ROOT, "tests", "cxx", "test_integration.bin")
-EXE_CAL = os.path.join(ROOT, "tests", "cxx", "test_integration_calibrate.bin")
+# programs compiled from reference sources are build products of oracle/_ref/ (never committed; they travel with the built tree)
+REF_BIN = os.path.join(ROOT, "oracle", "_ref")
+EXE = os.path.join(REF_BIN, "test_integration.bin")
+EXE_CAL = os.path.join(REF_BIN, "test_integration_calibrate.bin")
+RPATH_REL = "-Wl,-rpath,$ORIGIN/../../direct_visual_lidar_calibration_amd/csrc"  # libnidreg.so wherever the tree lies
 
 
 def build(scratch):
@@ -27,6 +30,7 @@ def build(scratch):
     for name in ("generic_camera_base.hpp", "generic_camera.hpp"):
         shutil.copy(os.path.join(REF, "include", "camera", name), inc)
     subprocess.check_call(["patch", "-p1", "-s", "-d", scratch, "-i", os.path.join(ROOT, "integration", "reference_camera.patch")])
+    os.makedirs(REF_BIN, exist_ok=True)
     if not os.path.exists(os.path.join(CSRC, "libnidreg.so")):
         import __graft_entry__
 
@@ -36,7 +40,7 @@ def build(scratch):
            "-I", os.path.join(ROOT, "oracle", "shim"),      # Eigen / ceres / OpenCV as this image knows them
            "-I", os.path.join(REF, "include"), "-I", os.path.join(ROOT, "include"),
            os.path.join(ROOT, "tests", "cxx", "test_integration.cpp"), os.path.join(REF, "src", "camera", "create_camera.cpp"),
-           "-L", CSRC, "-lnidreg", f"-Wl,-rpath,{CSRC}", "-o", EXE]
+           "-L", CSRC, "-lnidreg", f"-Wl,-rpath,{CSRC}", RPATH_REL, "-o", EXE]
     subprocess.check_call(cmd)
     return EXE
 
@@ -49,12 +53,12 @@ def build_calibrate(scratch):
            "-I", os.path.join(REF, "include"), "-I", os.path.join(ROOT, "include"),
            os.path.join(ROOT, "tests", "cxx", "test_integration_calibrate.cpp"), os.path.join(REF, "src", "vlcal", "calib", "visual_camera_calibration.cpp"),
            os.path.join(REF, "src", "camera", "create_camera.cpp"), os.path.join(REF, "src", "vlcal", "common", "estimate_fov.cpp"),
-           "-L", CSRC, "-lnidreg", f"-Wl,-rpath,{CSRC}", "-o", EXE_CAL]
+           "-L", CSRC, "-lnidreg", f"-Wl,-rpath,{CSRC}", RPATH_REL, "-o", EXE_CAL]
     subprocess.check_call(cmd)
     return EXE_CAL
 
 
-EXE_CAL_NP = os.path.join(ROOT, "tests", "cxx", "test_integration_calibrate_nopatch.bin")
+EXE_CAL_NP = os.path.join(REF_BIN, "test_integration_calibrate_nopatch.bin")
 
 
 def build_calibrate_nopatch():
@@ -65,12 +69,13 @@ def build_calibrate_nopatch():
         import __graft_entry__
 
         __graft_entry__.build()
+    os.makedirs(REF_BIN, exist_ok=True)
     cmd = ["g++", "-std=c++17", "-O1", "-DNIDREG_WITH_REFERENCE_DEPS", "-Wno-sign-compare", "-Wl,--allow-multiple-definition",
            "-I", os.path.join(ROOT, "integration", "include"), "-I", os.path.join(ROOT, "oracle", "shim"),
            "-I", os.path.join(REF, "include"), "-I", os.path.join(ROOT, "include"),
            os.path.join(ROOT, "tests", "cxx", "test_integration_calibrate.cpp"), os.path.join(REF, "src", "vlcal", "calib", "visual_camera_calibration.cpp"),
            os.path.join(ROOT, "integration", "src", "create_camera.cpp"), os.path.join(REF, "src", "vlcal", "common", "estimate_fov.cpp"),
-           "-L", CSRC, "-lnidreg", f"-Wl,-rpath,{CSRC}", "-o", EXE_CAL_NP]
+           "-L", CSRC, "-lnidreg", f"-Wl,-rpath,{CSRC}", RPATH_REL, "-o", EXE_CAL_NP]
     subprocess.check_call(cmd)
     return EXE_CAL_NP
 
@@ -147,7 +152,7 @@ def test_patch_applies_builds_and_cameras_expose_parameters(tmp_path):
 @pytest.mark.gpu
 def test_reference_cameras_feed_the_gpu_cost(tmp_path):
     if not os.path.exists(EXE):
-        pytest.skip("tests/cxx/test_integration.bin was not built (needs the reference tree; built by the CPU test)")
+        pytest.skip("oracle/_ref/test_integration.bin was not built (needs the reference tree; built by the CPU test)")
     import oracle_lib
     from direct_visual_lidar_calibration_amd import se3, synth
     from test_gpu_parity import CAMERAS
@@ -178,7 +183,7 @@ def test_reference_cameras_feed_the_gpu_cost(tmp_path):
 def test_reference_calibrate_drives_the_gpu_engine_without_any_header_patch(tmp_path):
     """Same as below through the patch-free route (replacement create_camera.cpp, all reference headers untouched)."""
     if not os.path.exists(EXE_CAL_NP):
-        pytest.skip("tests/cxx/test_integration_calibrate_nopatch.bin was not built (needs the reference tree)")
+        pytest.skip("oracle/_ref/test_integration_calibrate_nopatch.bin was not built (needs the reference tree)")
     from direct_visual_lidar_calibration_amd import se3
     from test_reference_golden import CASES
 
@@ -197,7 +202,7 @@ def test_reference_calibrate_drives_the_gpu_engine(tmp_path):
     drop-in headers ends where the reference's CPU build ends (fixture).  The binary is built where the reference tree
     is mounted and travels with the snapshot."""
     if not os.path.exists(EXE_CAL):
-        pytest.skip("tests/cxx/test_integration_calibrate.bin was not built (needs the reference tree)")
+        pytest.skip("oracle/_ref/test_integration_calibrate.bin was not built (needs the reference tree)")
     from direct_visual_lidar_calibration_amd import se3
     from test_reference_golden import CASES
 

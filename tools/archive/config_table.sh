@@ -3,7 +3,7 @@
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/config_table.jsonl
 : > $OUT
-run() { python $REPO/bench.py --steps 20 --warmup 3 --cpu-sample 500000 "$@" 2>/dev/null | tail -1 >> $OUT; }
+run() { python $REPO/bench.py --full --steps 20 --warmup 3 --cpu-sample 500000 "$@" 2>/dev/null | tail -1 >> $OUT; }
 run --points 100000 --camera pinhole_vga --bins 16
 run --points 10000000 --camera pinhole_1080p --bins 256
 run --points 10000000 --camera equirect_2k --bins 256

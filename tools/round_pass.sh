@@ -10,7 +10,7 @@
 #   run=<camera>:<points>[:<bins>]      tools/run_scene.py alone (event times, wall time) -> <camera>_<points>_run.json
 #   variants=<camera>:<points>:<v1,v2>  variants/libnidreg_<v>.so (tools/build_variants.sh) on that scene, same box -> variants.jsonl
 #   benchstats                          rocprofv3 --kernel-trace --stats around the headline bench command -> kernel_stats.json
-#   bench[=<bench.py arguments>]        python bench.py ... -> bench_line.json
+#   bench[=<bench.py arguments>]        python bench.py --full ... -> bench_line.json
 #   shardcost[=<bins>]                  tools/shard_cost.py (one-GPU protocol measurement) -> shard_cost_b<bins>.json
 #   sh=<command>                        anything else, logged to sh_<n>.txt
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
@@ -84,15 +84,15 @@ for l in open(sys.argv[1]):
 PY
       ;;
     benchstats)
-      (cd /tmp && timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$N -- python $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-config-legs > $O/bench_trace.log 2>&1); echo "rc=$?"
+      (cd /tmp && timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$N -- python $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-config-legs > $O/bench_trace.log 2>&1); echo "rc=$?"
       F=$(find $O/trace_$N -name "*kernel_stats.csv" | head -1)
       if [ -n "$F" ]; then
         grep -E "Name|nidreg" $F > $O/bench_kernel_stats.csv
-        python tools/kernel_stats_json.py $F $O/kernel_stats.json 10000000 1920 1080 256 fp64 "rocprofv3 --kernel-trace --stats -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-config-legs"
+        python tools/kernel_stats_json.py $F $O/kernel_stats.json 10000000 1920 1080 256 fp64 "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-config-legs"
       fi
       rm -rf $O/trace_$N ;;
     bench)
-      timeout 1200 python bench.py $ARG > $O/bench_line_$N.json 2> $O/bench_err_$N.txt; echo "rc=$?"; cut -c1-600 $O/bench_line_$N.json ;;
+      timeout 1200 python bench.py --full $ARG > $O/bench_line_$N.json 2> $O/bench_err_$N.txt; echo "rc=$?"; cut -c1-600 $O/bench_line_$N.json ;;
     shardcost)
       timeout 600 python tools/shard_cost.py ${ARG:-256} > $O/shard_cost_b${ARG:-256}.json 2> $O/shard_cost_err.txt; echo "rc=$?"; cat $O/shard_cost_b${ARG:-256}.json | head -c 1500 ;;
     sh)
