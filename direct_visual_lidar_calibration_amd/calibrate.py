@@ -51,9 +51,19 @@ class _Multi:
         return self.m(x, want_grad)
 
 
+def _upload(points, intensities, device):
+    """One pair's cloud to HBM: float32 ``(N, 3)`` + ``(N,)`` as stored (``Cloud.from_float32``, widened on the GPU), else the
+    ``(N, 4)`` float64 route."""
+    pts = np.asarray(points)
+    if pts.dtype == np.float32 and pts.ndim == 2 and pts.shape[1] == 3:
+        return nid.Cloud.from_float32(pts, intensities, device=device)
+    return nid.Cloud(points, intensities, device=device)
+
+
 def calibrate_pairs(proj, pairs, init_x, params, precision="fp64", stats=None):
     """The in-memory body of the command: ``pairs`` = [(image_u8 (H, W), points (N, 4), intensities (N,)), ...] as
-    ``VisualLiDARData`` holds them, ``init_x`` the Sophus-order ``T_camera_lidar`` 7-vector.  One upload per pair; every outer
+    ``VisualLiDARData`` holds them -- or (image_u8, xyz float32 (N, 3), intensities float32 (N,)) as the file stores them, uploaded
+    without a host widening pass -- ``init_x`` the Sophus-order ``T_camera_lidar`` 7-vector.  One upload per pair; every outer
     iteration culls + rebuilds its cost object on the device (visual_camera_calibration.cpp:76-85 / :201-206); every cost
     evaluation runs on the GPU.  Returns ``(x, VisualCameraCalibration)``; ``stats`` (optional dict) receives the wall-clock
     split: ``upload_s`` (clouds to HBM), ``build_s`` (culling + record build of every outer iteration), ``evaluations``."""
@@ -61,7 +71,7 @@ def calibrate_pairs(proj, pairs, init_x, params, precision="fp64", stats=None):
     if ndev <= 0:
         raise SystemExit("error: no MI355X / HIP device visible (the NID core has no CPU fallback)")
     t0 = time.perf_counter()
-    clouds = [nid.Cloud(p[1], p[2], device=k % ndev) for k, p in enumerate(pairs)]
+    clouds = [_upload(p[1], p[2], k % ndev) for k, p in enumerate(pairs)]
     images_f64 = [p[0].astype(np.float64) * (1.0 / 255.0) for p in pairs]  # convertTo(CV_64FC1, 1/255), :204
     upload_s = time.perf_counter() - t0
     size = (pairs[0][0].shape[1], pairs[0][0].shape[0])
@@ -114,13 +124,15 @@ def run(args, log=print):
         disable_z_buffer_culling=args.disable_culling, nid_bins=args.nid_bins, registration_type=args.registration_type, nelder_mead_init_step=args.nelder_mead_init_step,
         nelder_mead_convergence_criteria=args.nelder_mead_convergence_criteria)
     for b in bags:
-        log(f"loaded {b.bag_name}: image {b.image.shape[1]}x{b.image.shape[0]}, {b.points.shape[0]} points")
+        log(f"loaded {b.bag_name}: image {b.image.shape[1]}x{b.image.shape[0]}, {b.num_points} points")
     if args.dry_run:
         return config, init_x, None
 
     stats = {}
     t0 = time.time()
-    x, cal = calibrate_pairs(proj, [(b.image, b.points, b.intensities) for b in bags], init_x, params, precision=args.precision, stats=stats)
+    # float32 bags go up as stored (nid.Cloud.from_float32): the CLI never widens a cloud on the host
+    pairs = [(b.image, b.xyz_f32, b.intensities_f32) if b.xyz_f32 is not None else (b.image, b.points, b.intensities) for b in bags]
+    x, cal = calibrate_pairs(proj, pairs, init_x, params, precision=args.precision, stats=stats)
     elapsed = time.time() - t0
     ndev = stats["devices"]
     for entry in cal.log:

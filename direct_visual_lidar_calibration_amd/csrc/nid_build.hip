@@ -295,6 +295,47 @@ hipError_t mark_bins_device(const double* d_v, long long n, int B, unsigned char
 }
 
 // ------------------------------------------------------------------------------------------
+// float32 cloud ingest (nidreg_cloud_create_f32): the reference stores x y z intensity as four floats per vertex
+// (preprocess.cpp:161-169) and widens them to doubles after loading (visual_lidar_data.cpp:19-26).  Here only the float
+// records cross PCIe; one lane per point widens them into the cloud's (x y z 1) double + intensity layout.  float -> double
+// is exact: this TU keeps fp32 denormals (hipcc's default mode, no -fgpu-flush-denormals-to-zero), so v_cvt_f64_f32 sees
+// denormal inputs as they are; +-0, +-inf and NaN pass through.  kRec16: the stored 16 B record x y z intensity, one
+// 16 B load per lane (the staging base is hipMalloc-aligned).
+namespace {
+template <bool kRec16>
+__global__ __launch_bounds__(256) void k_cloud_widen(const unsigned char* __restrict__ src, long long pt_off, long long pt_stride, long long in_off, long long in_stride, long long n,
+                                                     double* __restrict__ pts, double* __restrict__ intensities) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float x, y, z, v;
+  if (kRec16) {
+    const float4 r = reinterpret_cast<const float4*>(src)[i];
+    x = r.x, y = r.y, z = r.z, v = r.w;
+  } else {
+    const float* p = reinterpret_cast<const float*>(src + pt_off + i * pt_stride);
+    x = p[0], y = p[1], z = p[2];
+    v = *reinterpret_cast<const float*>(src + in_off + i * in_stride);
+  }
+  double2* o = reinterpret_cast<double2*>(pts + 4 * i);
+  o[0] = make_double2(double(x), double(y));
+  o[1] = make_double2(double(z), 1.0);
+  intensities[i] = double(v);
+}
+}  // namespace
+
+hipError_t widen_cloud_device(const void* d_src, long long pt_off, long long pt_stride, long long in_off, long long in_stride, long long n, double* d_pts, double* d_int,
+                              hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  const unsigned grid = unsigned((n + 255) / 256);
+  const unsigned char* src = static_cast<const unsigned char*>(d_src);
+  if (pt_off == 0 && pt_stride == 16 && in_off == 12 && in_stride == 16 && (reinterpret_cast<uintptr_t>(src) & 15) == 0)
+    hipLaunchKernelGGL(k_cloud_widen<true>, dim3(grid), dim3(256), 0, stream, src, pt_off, pt_stride, in_off, in_stride, n, d_pts, d_int);
+  else
+    hipLaunchKernelGGL(k_cloud_widen<false>, dim3(grid), dim3(256), 0, stream, src, pt_off, pt_stride, in_off, in_stride, n, d_pts, d_int);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
 // Intensity rank equalisation (src/vlcal/preprocess/preprocess.cpp:464-473, preprocess_map.cpp): sort the
 // indices by intensity, then intensity[indices[i]] = floor(256 * double(i) / n) / 256.  The reference's
 // std::sort is unstable, so the rank order inside a group of EQUAL intensities is unspecified there;

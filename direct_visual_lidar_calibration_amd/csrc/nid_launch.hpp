@@ -157,6 +157,11 @@ size_t build_scratch_bytes(long long n, bool cull, int W, int H);
 hipError_t build_records_device(
   const double* d_pts, const double* d_intensities, long long n, const CullArgs* cull, int Bsrc, const uint16_t* d_lut, int GW, int NG, bool force_rec32, bool input_order, ScratchArena& arena,
   void** d_recs_out, int* rec64_out, std::vector<int64_t>& gcount, hipStream_t stream);
+// float32 cloud ingest (nidreg_cloud_create_f32, nid_build.hip k_cloud_widen): the n records staged at d_src -- x y z at byte
+// pt_off + i * pt_stride, the intensity at in_off + i * in_stride (all multiples of 4) -- widened exactly into a cloud's
+// d_pts (n x 4 doubles: x y z 1) and d_int (n doubles).  Asynchronous on `stream`.
+hipError_t widen_cloud_device(const void* d_src, long long pt_off, long long pt_stride, long long in_off, long long in_stride, long long n, double* d_pts, double* d_int,
+                              hipStream_t stream);
 // which of the B bins the n device-resident values occupy (used_host: B bytes)
 hipError_t mark_bins_device(const double* d_v, long long n, int B, unsigned char* used_host);
 

@@ -82,6 +82,65 @@ int nidreg_cloud_create(int device_id, const double* points, int64_t point_strid
   return NIDREG_OK;
 }
 
+// The cloud as the reference stores it (float x y z + float intensity, preprocess.cpp:161-169): only the float bytes cross
+// PCIe -- the one span covering both arrays when they interleave, else the two spans -- into a staging buffer that
+// k_cloud_widen (nid_build.hip) widens into the same d_pts / d_int nidreg_cloud_create fills (visual_lidar_data.cpp:19-26
+// widens on the host).  Plain pageable hipMemcpy: a pinned / staged upload was not faster (profiles/r06_experiments.md §6).
+int nidreg_cloud_create_f32(int device_id, const float* points, int64_t point_stride, const float* intensities, int64_t intensity_stride, int64_t num_points, nidreg_cloud** out) {
+  if (!out) return fail(NIDREG_ERR_INVALID, "nidreg_cloud_create_f32: null out");
+  *out = nullptr;
+  if (num_points < 0 || num_points > int64_t(INT_MAX)) return fail(NIDREG_ERR_INVALID, "nidreg_cloud_create_f32: num_points must be in [0, INT_MAX]");
+  if (num_points > 0 && (!points || !intensities)) return fail(NIDREG_ERR_INVALID, "nidreg_cloud_create_f32: null points / intensities");
+  if (point_stride < 12 || intensity_stride < 4) return fail(NIDREG_ERR_INVALID, "nidreg_cloud_create_f32: point_stride must be >= 12 and intensity_stride >= 4 bytes");
+  if (point_stride % 4 || intensity_stride % 4 || reinterpret_cast<uintptr_t>(points) % 4 || reinterpret_cast<uintptr_t>(intensities) % 4)
+    return fail(NIDREG_ERR_INVALID, "nidreg_cloud_create_f32: strides and pointers must be 4-byte aligned");
+  if (num_points > 0 && (point_stride > INT64_MAX / num_points || intensity_stride > INT64_MAX / num_points))
+    return fail(NIDREG_ERR_INVALID, "nidreg_cloud_create_f32: stride x num_points overflows");
+  if (device_id < 0) return fail(NIDREG_ERR_INVALID, "nidreg_cloud_create_f32: device_id out of range");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(NIDREG_ERR_NO_DEVICE, "nidreg_cloud_create_f32: no HIP device");
+  if (device_id >= ndev) return fail(NIDREG_ERR_INVALID, "nidreg_cloud_create_f32: device_id out of range");
+  HIP_TRY(hipSetDevice(device_id));
+  nidreg_cloud* c = new nidreg_cloud();
+  c->device = device_id;
+  c->n = num_points;
+  const size_t n1 = size_t(std::max<int64_t>(num_points, 1));
+  unsigned char* d_stage = nullptr;
+  hipError_t e = hipMalloc(&c->d_pts, n1 * 32);
+  if (e == hipSuccess) e = hipMalloc(&c->d_int, n1 * 8);
+  if (e == hipSuccess && num_points > 0) {
+    const uintptr_t p0 = reinterpret_cast<uintptr_t>(points), p1 = p0 + uintptr_t(num_points - 1) * uintptr_t(point_stride) + 12;
+    const uintptr_t q0 = reinterpret_cast<uintptr_t>(intensities), q1 = q0 + uintptr_t(num_points - 1) * uintptr_t(intensity_stride) + 4;
+    long long pt_off = 0, in_off = 0;
+    if (p0 < q1 && q0 < p1) {  // interleaved records: the one covering span
+      const uintptr_t lo = std::min(p0, q0), hi = std::max(p1, q1);
+      pt_off = (long long)(p0 - lo);
+      in_off = (long long)(q0 - lo);
+      e = hipMalloc(&d_stage, size_t(hi - lo));
+      if (e == hipSuccess) e = hipMemcpy(d_stage, reinterpret_cast<const void*>(lo), size_t(hi - lo), hipMemcpyHostToDevice);
+    } else {  // separate arrays (SoA): two spans, the intensities' at a 256-byte boundary
+      in_off = (long long)((p1 - p0 + 255) & ~uintptr_t(255));
+      e = hipMalloc(&d_stage, size_t(in_off) + size_t(q1 - q0));
+      if (e == hipSuccess) e = hipMemcpy(d_stage, points, size_t(p1 - p0), hipMemcpyHostToDevice);
+      if (e == hipSuccess) e = hipMemcpy(d_stage + in_off, intensities, size_t(q1 - q0), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = widen_cloud_device(d_stage, pt_off, point_stride, in_off, intensity_stride, num_points, c->d_pts, c->d_int, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  }
+  if (d_stage) {
+    const hipError_t ef = hipFree(d_stage);
+    if (e == hipSuccess) e = ef;
+  }
+  if (e != hipSuccess) {
+    if (c->d_pts) (void)hipFree(c->d_pts);
+    if (c->d_int) (void)hipFree(c->d_int);
+    delete c;
+    return fail(NIDREG_ERR_HIP, std::string("nidreg_cloud_create_f32: ") + hipGetErrorString(e));
+  }
+  *out = c;
+  return NIDREG_OK;
+}
+
 void nidreg_cloud_destroy(nidreg_cloud* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);

@@ -15,6 +15,7 @@ here                                    reference
 
 Pure host code (numpy + zlib + json); nothing here is on the per-evaluation path.
 """
+import functools
 import json
 import os
 import struct
@@ -31,13 +32,9 @@ _PLY_TYPES = {
 }
 
 
-def read_ply(path):
-    """Vertex positions and intensities of a PLY file.  Returns ``(points (n, 4) float64 homogeneous,
-    intensities (n,) float64 or None)`` -- ``FrameCPU(ply->vertices)`` + ``add_intensities``
-    (visual_lidar_data.cpp:25-26).  ascii, binary_little_endian and binary_big_endian are accepted;
-    only the vertex element is read."""
-    with open(path, "rb") as f:
-        data = f.read()
+def _parse_ply_header(data, path):
+    """``(format, elements, body offset)`` of a PLY file whose first bytes (the whole header at least) are ``data``;
+    elements = [(name, count, [(prop name, dtype code) | None for lists])]."""
     end = data.find(b"end_header")
     if not data.startswith(b"ply") or end < 0:
         raise ValueError(f"{path}: not a PLY file")
@@ -67,6 +64,20 @@ def read_ply(path):
                 elements[-1][2].append((tok[2], _PLY_TYPES[tok[1]]))
     if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
         raise ValueError(f"{path}: unsupported PLY format {fmt}")
+    return fmt, elements, body
+
+
+_INTENSITY_NAMES = ("intensity", "scalar_intensity", "intensities")
+
+
+def read_ply(path):
+    """Vertex positions and intensities of a PLY file.  Returns ``(points (n, 4) float64 homogeneous,
+    intensities (n,) float64 or None)`` -- ``FrameCPU(ply->vertices)`` + ``add_intensities``
+    (visual_lidar_data.cpp:25-26).  ascii, binary_little_endian and binary_big_endian are accepted;
+    only the vertex element is read."""
+    with open(path, "rb") as f:
+        data = f.read()
+    fmt, elements, body = _parse_ply_header(data, path)
     offset = body
     for name, count, props in elements:
         if name == "vertex":
@@ -90,7 +101,7 @@ def read_ply(path):
             pts = np.ones((count, 4), dtype=np.float64)
             pts[:, 0], pts[:, 1], pts[:, 2] = cols["x"], cols["y"], cols["z"]
             inten = None
-            for k in ("intensity", "scalar_intensity", "intensities"):
+            for k in _INTENSITY_NAMES:
                 if k in cols:
                     inten = np.ascontiguousarray(cols[k], dtype=np.float64)
                     break
@@ -104,6 +115,47 @@ def read_ply(path):
                 raise ValueError(f"{path}: list element '{name}' precedes the vertices")
             offset += count * sum(np.dtype(c).itemsize for _, c in props)
     raise ValueError(f"{path}: no vertex element")
+
+
+def read_ply_float32(path):
+    """The cloud as ``preprocess`` stores it (preprocess.cpp:161-169), without a widening pass: ``(xyz (n, 3), intensities (n,))``,
+    float32 views over ONE read of the file's vertex block (rows strided by the record size; both alias the same buffer), for
+    ``nid.Cloud.from_float32``.  ``None`` -- use ``read_ply`` -- unless the file is binary_little_endian and its vertex element has
+    float ``x y z`` (consecutive) and a float intensity property (the one ``read_ply`` picks) at 4-byte aligned offsets.
+    Widened, the views equal ``read_ply``'s arrays bit for bit."""
+    with open(path, "rb") as f:
+        head = f.read(1 << 16)
+        while b"end_header" not in head or head.find(b"\n", head.find(b"end_header")) < 0:
+            more = f.read(1 << 16)
+            if not more:
+                break
+            head += more
+        size = f.seek(0, os.SEEK_END)
+    fmt, elements, offset = _parse_ply_header(head, path)
+    if fmt != "binary_little_endian":
+        return None
+    for name, count, props in elements:
+        if any(p is None for p in props):
+            return None
+        if name != "vertex":
+            offset += count * sum(np.dtype(c).itemsize for _, c in props)  # an element stored before the vertices
+            continue
+        dt = np.dtype([(n, "<" + c) for n, c in props])
+        key = next((k for k in _INTENSITY_NAMES if k in dt.names), None)
+        if key is None or any(k not in dt.names or dt[k] != np.dtype("<f4") for k in ("x", "y", "z", key)):
+            return None
+        ox, oi = dt.fields["x"][1], dt.fields[key][1]
+        if dt.fields["y"][1] != ox + 4 or dt.fields["z"][1] != ox + 8 or dt.itemsize % 4 or ox % 4 or oi % 4:
+            return None
+        if offset + count * dt.itemsize > size:
+            return None  # (read_ply says: truncated)
+        if count == 0:
+            return np.zeros((0, 3), dtype=np.float32), np.zeros(0, dtype=np.float32)
+        raw = np.fromfile(path, dtype=np.uint8, count=count * dt.itemsize, offset=offset)  # not a memmap: no page faults inside the upload
+        xyz = np.ndarray((count, 3), dtype="<f4", buffer=raw, offset=ox, strides=(dt.itemsize, 4))
+        inten = np.ndarray((count,), dtype="<f4", buffer=raw, offset=oi, strides=(dt.itemsize,))
+        return xyz, inten
+    return None
 
 
 def write_ply(path, points, intensities):
@@ -331,7 +383,11 @@ def T_camera_lidar_to_tum(x):
 
 
 class VisualLiDARData:
-    """``vlcal::VisualLiDARData``: one bag's image (8-bit gray) and cloud (points (n,4), intensities)."""
+    """``vlcal::VisualLiDARData``: one bag's image (8-bit gray) and cloud (points (n,4), intensities).
+
+    A cloud stored as float32 records (what ``preprocess`` writes) is kept as read: ``xyz_f32`` / ``intensities_f32``
+    (``read_ply_float32``), uploaded as such by ``calibrate``; ``points`` / ``intensities`` are then widened on first use (and
+    cached), with the values ``read_ply`` gives.  Any other file loads eagerly (``xyz_f32`` is ``None``)."""
 
     def __init__(self, data_path, bag_name):
         png = os.path.join(data_path, bag_name + ".png")
@@ -342,9 +398,26 @@ class VisualLiDARData:
             raise FileNotFoundError(f"warning: failed to load {ply}")
         self.bag_name = bag_name
         self.image = read_png_gray(png)
-        self.points, self.intensities = read_ply(ply)
-        if self.intensities is None:
-            raise ValueError(f"{ply}: no intensity property")
+        f32 = read_ply_float32(ply)
+        if f32 is not None:
+            self.xyz_f32, self.intensities_f32 = f32
+        else:
+            self.xyz_f32 = self.intensities_f32 = None
+            self.points, self.intensities = read_ply(ply)
+            if self.intensities is None:
+                raise ValueError(f"{ply}: no intensity property")
+        self.num_points = int(self.xyz_f32.shape[0] if f32 is not None else self.points.shape[0])
+
+    # float32 bags only (an eagerly loaded bag has these as plain attributes, which take precedence)
+    @functools.cached_property
+    def points(self):
+        pts = np.ones((self.num_points, 4), dtype=np.float64)
+        pts[:, :3] = self.xyz_f32
+        return pts
+
+    @functools.cached_property
+    def intensities(self):
+        return np.ascontiguousarray(self.intensities_f32, dtype=np.float64)
 
 
 def load_dataset(data_path, first_n_bags=None):

@@ -109,6 +109,38 @@ class Cloud:
         self.device = int(device)
         self.num_points = points.shape[0]
 
+    @classmethod
+    def from_float32(cls, xyz, intensities, device=0):
+        """The same device cloud from the float32 records as ``preprocess`` stores them (preprocess.cpp:161-169):
+        ``xyz`` an (N, 3) float32 view whose rows may be strided, ``intensities`` an (N,) float32 view of any stride; both may
+        alias one record buffer (``dataset.read_ply_float32``).  Only the float bytes are uploaded; the GPU widens them
+        (``nidreg_cloud_create_f32``) into exactly the doubles ``Cloud(points, intensities)`` would hold."""
+        xyz = np.asarray(xyz)
+        intensities = np.asarray(intensities)
+        for a in (xyz, intensities):
+            if a.dtype.kind != "f" or a.dtype.itemsize != 4:
+                raise ValueError("xyz and intensities must be float32")
+            if not a.dtype.isnative:
+                raise ValueError("xyz and intensities must be in native byte order")
+        if xyz.ndim != 2 or xyz.shape[1] != 3 or intensities.shape != (xyz.shape[0],):
+            raise ValueError("xyz must be (N, 3) and intensities (N,)")
+        n = xyz.shape[0]
+        if n:  # (numpy's strides of an empty array are arbitrary)
+            if any(s % 4 for s in xyz.strides + intensities.strides):
+                raise ValueError("strides must be multiples of 4 bytes")
+            if xyz.strides[1] != 4:
+                raise ValueError("the x y z of a point must be three consecutive floats (xyz.strides[1] == 4)")
+        lib = _lib.load()
+        pstride, istride = (xyz.strides[0], intensities.strides[0]) if n > 1 else (12, 4)  # (one point: the stride is never used)
+        c = ctypes.c_void_p()
+        _lib.check(lib.nidreg_cloud_create_f32(int(device), xyz.ctypes.data, pstride, intensities.ctypes.data, istride, n, ctypes.byref(c)), "nidreg_cloud_create_f32")
+        self = cls.__new__(cls)
+        self._lib = lib
+        self.c = c
+        self.device = int(device)
+        self.num_points = n
+        return self
+
     def close(self):
         if getattr(self, "c", None):
             self._lib.nidreg_cloud_destroy(self.c)

@@ -29,6 +29,10 @@
  *                            column groups and the points that fall into them) and every GPU stores its columns of the
  *                            integer histogram into every other GPU's replica, once per evaluation (the reference's calibrate is a
  *                            single process, src/calibrate.cpp:117-120)
+ *   nidreg_cloud_create_f32  the float32 cloud as stored: preprocess.cpp writes x y z intensity as four floats per
+ *                            vertex (src/vlcal/preprocess/preprocess.cpp:161-169); VisualLiDARData widens them to
+ *                            doubles on the host after loading (src/vlcal/common/visual_lidar_data.cpp:19-26) --
+ *                            here the floats are uploaded and widened on the GPU
  *   nidreg_destroy           ~NIDCost / ~CostCalculatorNID
  *
  * Conventions
@@ -180,6 +184,15 @@ void nidreg_destroy(nidreg_handle* h);
  * column groups device to device. */
 typedef struct nidreg_cloud nidreg_cloud;
 int nidreg_cloud_create(int device_id, const double* points, int64_t point_stride, const double* intensities, int64_t num_points, nidreg_cloud** out);
+/* The same cloud from float32 records: x y z (three consecutive floats) every point_stride bytes, one float intensity every
+ * intensity_stride bytes -- the stored PLY record (both pointers inside one 16 B or wider record, both strides = the record
+ * size) or separate arrays (glk PLYData: vertices stride 12, intensities stride 4).  Only the float bytes are uploaded (the
+ * one span covering both arrays when they interleave, else the two spans); the GPU widens them exactly into the layout
+ * nidreg_cloud_create makes (x y z 1 doubles + double intensities), so every handle built from it has the same bits.
+ * NIDREG_ERR_INVALID, before any device call: num_points outside [0, INT_MAX], a NULL pointer with num_points > 0, strides
+ * below 12 / 4 bytes, strides or pointers not 4-byte aligned, a negative device_id (out of range: after the device count). */
+int nidreg_cloud_create_f32(int device_id, const float* points, int64_t point_stride, const float* intensities, int64_t intensity_stride, int64_t num_points,
+                            nidreg_cloud** out);
 void nidreg_cloud_destroy(nidreg_cloud* cloud);
 int nidreg_create_from_cloud(const nidreg_desc* desc, const nidreg_cloud* cloud, const double* T_camera_lidar, double min_z, int enable_depth_buffer_culling, nidreg_handle** out);
 

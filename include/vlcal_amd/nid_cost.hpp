@@ -37,6 +37,15 @@ public:
       throw std::runtime_error(std::string("vlcal::DeviceCloud: ") + nidreg_last_error());
     cloud = std::shared_ptr<nidreg_cloud>(c, &nidreg_cloud_destroy);
   }
+  // The float32 cloud as loaded, before the widening of visual_lidar_data.cpp:19-26: x y z every point_stride bytes and one
+  // intensity every intensity_stride bytes -- glk::PLYData's vertices / intensities (strides 12 / 4) or the stored 16 B PLY
+  // record (both strides 16).  Only the floats are uploaded; the GPU widens them (nidreg_cloud_create_f32): same handles.
+  DeviceCloud(const float* points, const int64_t point_stride, const float* intensities, const int64_t intensity_stride, const int64_t num_points, const int device_id = 0) {
+    nidreg_cloud* c = nullptr;
+    if (nidreg_cloud_create_f32(device_id, points, point_stride, intensities, intensity_stride, num_points, &c) != NIDREG_OK)
+      throw std::runtime_error(std::string("vlcal::DeviceCloud: ") + nidreg_last_error());
+    cloud = std::shared_ptr<nidreg_cloud>(c, &nidreg_cloud_destroy);
+  }
   const nidreg_cloud* get() const { return cloud.get(); }
 
 private:
