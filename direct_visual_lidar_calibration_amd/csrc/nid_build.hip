@@ -163,6 +163,7 @@ hipError_t build_records_device(
   int* d_first = nullptr;  // NG + 1 firsts, then the not-lossless flag
   void* d_tmp = nullptr;
   size_t tmp_bytes = 0;
+  DeviceBuf recs;
   void* d_recs = nullptr;
   std::vector<int> first(size_t(NG) + 2, -1);
   const unsigned grid = unsigned((n + 255) / 256);
@@ -228,7 +229,8 @@ hipError_t build_records_device(
   }
   {
     const size_t rec_bytes = rec64 ? sizeof(Rec64) : sizeof(Rec32);
-    BUILD_TRY(hipMalloc(&d_recs, size_t(kept > 0 ? kept : 1) * rec_bytes + 64));
+    BUILD_TRY(recs.alloc(size_t(kept > 0 ? kept : 1) * rec_bytes + 64));
+    d_recs = recs.as<void>();
     if (kept > 0) {
       const unsigned g2 = unsigned((kept + 255) / 256);
       if (rec64)
@@ -239,12 +241,10 @@ hipError_t build_records_device(
       BUILD_TRY(hipStreamSynchronize(stream));
     }
   }
-  *d_recs_out = d_recs;
-  d_recs = nullptr;
+  *d_recs_out = recs.release();
   *rec64_out = rec64;
 done:
 #undef CARVE
-  if (d_recs) (void)hipFree(d_recs);
   return e;
 }
 
@@ -281,16 +281,16 @@ hipError_t build_bin_image_device(const void* d_src, int is_f64, long long row_s
 
 // which of the B bins the n device-resident values v occupy (bins > 256 on a device-resident cloud: nidreg_plan.hip resolve_wide_bins)
 hipError_t mark_bins_device(const double* d_v, long long n, int B, unsigned char* used_host) {
-  unsigned char* d_used = nullptr;
-  hipError_t e = hipMalloc(&d_used, size_t(B));
+  DeviceBuf used;
+  hipError_t e = used.alloc(size_t(B));
   if (e != hipSuccess) return e;
+  unsigned char* d_used = used.as<unsigned char>();
   e = hipMemset(d_used, 0, size_t(B));
   if (e == hipSuccess && n > 0) {
     hipLaunchKernelGGL(k_mark_bins, dim3(unsigned((n + 255) / 256)), dim3(256), 0, hipStream_t(nullptr), d_v, n, B, d_used);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(used_host, d_used, size_t(B), hipMemcpyDeviceToHost);
-  (void)hipFree(d_used);
   return e;
 }
 
@@ -359,29 +359,26 @@ __global__ __launch_bounds__(256) void k_eq_scatter(const unsigned int* __restri
 hipError_t equalize_intensities_device(double* d_intensities, long long n, hipStream_t stream) {
   if (n <= 0) return hipSuccess;
   hipError_t e = hipSuccess;
+  DeviceBuf keys, keys2, idx, idx2, tmp;
   unsigned long long *d_keys = nullptr, *d_keys2 = nullptr;
   unsigned int *d_idx = nullptr, *d_idx2 = nullptr;
-  void* d_tmp = nullptr;
   size_t tmp_bytes = 0;
   const unsigned grid = unsigned((n + 255) / 256);
-  BUILD_TRY(hipMalloc(&d_keys, size_t(n) * 8));
-  BUILD_TRY(hipMalloc(&d_keys2, size_t(n) * 8));
-  BUILD_TRY(hipMalloc(&d_idx, size_t(n) * 4));
-  BUILD_TRY(hipMalloc(&d_idx2, size_t(n) * 4));
+  BUILD_TRY(keys.alloc(size_t(n) * 8));
+  BUILD_TRY(keys2.alloc(size_t(n) * 8));
+  BUILD_TRY(idx.alloc(size_t(n) * 4));
+  BUILD_TRY(idx2.alloc(size_t(n) * 4));
+  d_keys = keys.as<unsigned long long>(), d_keys2 = keys2.as<unsigned long long>();
+  d_idx = idx.as<unsigned int>(), d_idx2 = idx2.as<unsigned int>();
   hipLaunchKernelGGL(k_eq_keys, dim3(grid), dim3(256), 0, stream, d_intensities, n, d_keys, d_idx);
   BUILD_TRY(hipGetLastError());
   BUILD_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, size_t(n), 0, 64, stream));
-  BUILD_TRY(hipMalloc(&d_tmp, tmp_bytes));
-  BUILD_TRY(rocprim::radix_sort_pairs(d_tmp, tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, size_t(n), 0, 64, stream));
+  BUILD_TRY(tmp.alloc(tmp_bytes));
+  BUILD_TRY(rocprim::radix_sort_pairs(tmp.as<void>(), tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, size_t(n), 0, 64, stream));
   hipLaunchKernelGGL(k_eq_scatter, dim3(grid), dim3(256), 0, stream, d_idx2, n, d_intensities);
   BUILD_TRY(hipGetLastError());
   BUILD_TRY(hipStreamSynchronize(stream));
 done:
-  if (d_keys) (void)hipFree(d_keys);
-  if (d_keys2) (void)hipFree(d_keys2);
-  if (d_idx) (void)hipFree(d_idx);
-  if (d_idx2) (void)hipFree(d_idx2);
-  if (d_tmp) (void)hipFree(d_tmp);
   return e;
 }
 

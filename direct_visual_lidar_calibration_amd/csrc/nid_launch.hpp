@@ -8,9 +8,11 @@
 #include <stdint.h>
 
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "nid_multi.hpp"
+#include "../../include/nidreg.h"
 
 namespace nidreg {
 
@@ -117,6 +119,68 @@ hipError_t equalize_intensities_device(double* d_intensities, long long n, hipSt
 // error text of the calling thread (nidreg_last_error); returns `code`
 int fail(int code, const std::string& msg);
 
+#define HIP_TRY(expr)                                                                                   \
+  do {                                                                                                  \
+    hipError_t _e = (expr);                                                                             \
+    if (_e != hipSuccess) return fail(NIDREG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+  } while (0)
+
+// (internal to libnidreg.so: these helpers add nothing to its dynamic symbol table)
+#define NIDREG_HIDDEN __attribute__((visibility("hidden")))
+
+// Move-only owner of ONE device allocation (hipMalloc, or fine-grained hipExtMallocWithFlags: the shard histogram replicas and
+// exchange blocks; hipFree releases both).  The destructor frees and ignores the error; reset() reports it.  Whoever destroys an
+// owner makes sure first that no kernel still uses the memory (free_handle says how a handle does).
+class NIDREG_HIDDEN DeviceBuf {
+ public:
+  DeviceBuf() = default;
+  DeviceBuf(DeviceBuf&& o) noexcept : p_(o.release()) {}
+  DeviceBuf& operator=(DeviceBuf&& o) noexcept {  // (frees what it held AFTER `o` was allocated: a table regrow keeps the old one on failure)
+    if (this != &o) adopt(o.release());
+    return *this;
+  }
+  DeviceBuf(const DeviceBuf&) = delete;
+  DeviceBuf& operator=(const DeviceBuf&) = delete;
+  ~DeviceBuf() { (void)reset(); }
+  hipError_t alloc(size_t bytes) { return (void)reset(), hipMalloc(&p_, bytes); }
+  hipError_t alloc_finegrained(size_t bytes) { return (void)reset(), hipExtMallocWithFlags(&p_, bytes, hipDeviceMallocFinegrained); }
+  void adopt(void* p) { (void)reset(), p_ = p; }  // a hipMalloc'ed pointer handed over as "caller owns"
+  void* release() { return std::exchange(p_, nullptr); }
+  hipError_t reset() { return p_ ? hipFree(release()) : hipSuccess; }
+  template <typename T = void> T* as() const { return static_cast<T*>(p_); }
+  explicit operator bool() const { return p_ != nullptr; }
+ private:
+  void* p_ = nullptr;
+};
+// ... and of one host-mapped block that does not come from the per-device pool (nidreg_internal.hpp ResourcePool)
+class NIDREG_HIDDEN HostBuf {
+ public:
+  HostBuf() = default;
+  HostBuf(const HostBuf&) = delete;
+  HostBuf& operator=(const HostBuf&) = delete;
+  ~HostBuf() { reset(); }
+  hipError_t alloc(size_t bytes, unsigned flags) { return reset(), hipHostMalloc(&p_, bytes, flags); }
+  void reset() {
+    if (p_) (void)hipHostFree(std::exchange(p_, nullptr));
+  }
+  template <typename T = void> T* as() const { return static_cast<T*>(p_); }
+ private:
+  void* p_ = nullptr;
+};
+
+// entry points that take a device id: count -> range -> hipSetDevice, with the caller's name `who` in the error text
+NIDREG_HIDDEN inline int count_devices(const char* who, int* ndev, const char* note = "") {
+  if (hipGetDeviceCount(ndev) != hipSuccess || *ndev <= 0) return fail(NIDREG_ERR_NO_DEVICE, std::string(who) + ": no HIP device" + note);
+  return NIDREG_OK;
+}
+NIDREG_HIDDEN inline int use_device(const char* who, int device_id, const char* note = "") {
+  int ndev = 0;
+  if (const int rc = count_devices(who, &ndev, note)) return rc;
+  if (device_id < 0 || device_id >= ndev) return fail(NIDREG_ERR_INVALID, std::string(who) + ": device_id out of range");
+  HIP_TRY(hipSetDevice(device_id));
+  return NIDREG_OK;
+}
+
 // view-culling parameters for the device-side record build (all host values; T = rows of the 4x4)
 struct CullArgs {
   int model;
@@ -152,7 +216,7 @@ size_t build_scratch_bytes(long long n, bool cull, int W, int H);
 // [cull ->] bucket -> Morton sort -> gather on the device (nid_build.hip).  d_pts: n x 4 doubles (x y z 1),
 // cull nullable.  input_order: keep the caller's order inside each column group (stable sort on the group bits
 // only) instead of the Morton order.  Temporaries come from `arena` (reserved by the caller for at least
-// build_scratch_bytes).  Returns the record buffer (hipMalloc, caller owns), its type, and the column-group offsets.
+// build_scratch_bytes).  Returns the record buffer (hipMalloc, caller owns: DeviceBuf::adopt), its type, and the column-group offsets.
 // Bsrc = the caller's bin count (bin_points = clamp(int(intensity * Bsrc))); d_lut (nullable; bins > 256): occupied bin -> compact bin.
 hipError_t build_records_device(
   const double* d_pts, const double* d_intensities, long long n, const CullArgs* cull, int Bsrc, const uint16_t* d_lut, int GW, int NG, bool force_rec32, bool input_order, ScratchArena& arena,

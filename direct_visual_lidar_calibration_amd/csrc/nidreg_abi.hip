@@ -50,35 +50,33 @@ int nidreg_create(const nidreg_desc* d, nidreg_handle** out) {
   return create_done(create_impl(d, nullptr, nullptr, 0.0, 0, CreateOpts(), out), out);
 }
 
-int nidreg_cloud_create(int device_id, const double* points, int64_t point_stride, const double* intensities, int64_t num_points, nidreg_cloud** out) {
-  if (!out || num_points < 0 || num_points > int64_t(INT_MAX) || (num_points > 0 && (!points || !intensities))) return fail(NIDREG_ERR_INVALID, "nidreg_cloud_create: bad argument");
-  *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(NIDREG_ERR_NO_DEVICE, "nidreg_cloud_create: no HIP device");
-  if (device_id < 0 || device_id >= ndev) return fail(NIDREG_ERR_INVALID, "nidreg_cloud_create: device_id out of range");
-  HIP_TRY(hipSetDevice(device_id));
-  nidreg_cloud* c = new nidreg_cloud();
+// what nidreg_cloud_create and nidreg_cloud_create_f32 share: the device, the cloud object and its two arrays (`who` = the entry point's name)
+static int cloud_alloc(const char* who, int device_id, int64_t num_points, std::unique_ptr<nidreg_cloud>& c) {
+  if (const int rc = use_device(who, device_id)) return rc;
+  c.reset(new nidreg_cloud());
   c->device = device_id;
   c->n = num_points;
   const size_t n1 = size_t(std::max<int64_t>(num_points, 1));
-  hipError_t e = hipMalloc(&c->d_pts, n1 * 32);
-  if (e == hipSuccess) e = hipMalloc(&c->d_int, n1 * 8);
+  HIP_TRY(c->d_pts.alloc(n1 * 32));
+  HIP_TRY(c->d_int.alloc(n1 * 8));
+  return NIDREG_OK;
+}
+
+int nidreg_cloud_create(int device_id, const double* points, int64_t point_stride, const double* intensities, int64_t num_points, nidreg_cloud** out) {
+  if (!out || num_points < 0 || num_points > int64_t(INT_MAX) || (num_points > 0 && (!points || !intensities))) return fail(NIDREG_ERR_INVALID, "nidreg_cloud_create: bad argument");
+  *out = nullptr;
+  std::unique_ptr<nidreg_cloud> c;
+  if (const int rc = cloud_alloc("nidreg_cloud_create", device_id, num_points, c)) return rc;
   const int64_t stride = point_stride > 0 ? point_stride : 32;
-  if (e == hipSuccess && num_points > 0) {
+  if (num_points > 0) {
     if (stride == 32) {
-      e = hipMemcpy(c->d_pts, points, size_t(num_points) * 32, hipMemcpyHostToDevice);
+      HIP_TRY(hipMemcpy(c->d_pts.as<void>(), points, size_t(num_points) * 32, hipMemcpyHostToDevice));
     } else {
-      e = hipMemcpy2D(c->d_pts, 32, points, size_t(stride), 32, size_t(num_points), hipMemcpyHostToDevice);
+      HIP_TRY(hipMemcpy2D(c->d_pts.as<void>(), 32, points, size_t(stride), 32, size_t(num_points), hipMemcpyHostToDevice));
     }
-    if (e == hipSuccess) e = hipMemcpy(c->d_int, intensities, size_t(num_points) * 8, hipMemcpyHostToDevice);
+    HIP_TRY(hipMemcpy(c->d_int.as<void>(), intensities, size_t(num_points) * 8, hipMemcpyHostToDevice));
   }
-  if (e != hipSuccess) {
-    if (c->d_pts) (void)hipFree(c->d_pts);
-    if (c->d_int) (void)hipFree(c->d_int);
-    delete c;
-    return fail(NIDREG_ERR_HIP, std::string("nidreg_cloud_create: ") + hipGetErrorString(e));
-  }
-  *out = c;
+  *out = c.release();
   return NIDREG_OK;
 }
 
@@ -96,56 +94,38 @@ int nidreg_cloud_create_f32(int device_id, const float* points, int64_t point_st
     return fail(NIDREG_ERR_INVALID, "nidreg_cloud_create_f32: strides and pointers must be 4-byte aligned");
   if (num_points > 0 && (point_stride > INT64_MAX / num_points || intensity_stride > INT64_MAX / num_points))
     return fail(NIDREG_ERR_INVALID, "nidreg_cloud_create_f32: stride x num_points overflows");
+  // (a negative device id is refused BEFORE the device count is asked for: without a GPU it reports a bad argument, not a missing device)
   if (device_id < 0) return fail(NIDREG_ERR_INVALID, "nidreg_cloud_create_f32: device_id out of range");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(NIDREG_ERR_NO_DEVICE, "nidreg_cloud_create_f32: no HIP device");
-  if (device_id >= ndev) return fail(NIDREG_ERR_INVALID, "nidreg_cloud_create_f32: device_id out of range");
-  HIP_TRY(hipSetDevice(device_id));
-  nidreg_cloud* c = new nidreg_cloud();
-  c->device = device_id;
-  c->n = num_points;
-  const size_t n1 = size_t(std::max<int64_t>(num_points, 1));
-  unsigned char* d_stage = nullptr;
-  hipError_t e = hipMalloc(&c->d_pts, n1 * 32);
-  if (e == hipSuccess) e = hipMalloc(&c->d_int, n1 * 8);
-  if (e == hipSuccess && num_points > 0) {
+  std::unique_ptr<nidreg_cloud> c;
+  if (const int rc = cloud_alloc("nidreg_cloud_create_f32", device_id, num_points, c)) return rc;
+  if (num_points > 0) {
     const uintptr_t p0 = reinterpret_cast<uintptr_t>(points), p1 = p0 + uintptr_t(num_points - 1) * uintptr_t(point_stride) + 12;
     const uintptr_t q0 = reinterpret_cast<uintptr_t>(intensities), q1 = q0 + uintptr_t(num_points - 1) * uintptr_t(intensity_stride) + 4;
     long long pt_off = 0, in_off = 0;
+    DeviceBuf stage;
     if (p0 < q1 && q0 < p1) {  // interleaved records: the one covering span
       const uintptr_t lo = std::min(p0, q0), hi = std::max(p1, q1);
       pt_off = (long long)(p0 - lo);
       in_off = (long long)(q0 - lo);
-      e = hipMalloc(&d_stage, size_t(hi - lo));
-      if (e == hipSuccess) e = hipMemcpy(d_stage, reinterpret_cast<const void*>(lo), size_t(hi - lo), hipMemcpyHostToDevice);
+      HIP_TRY(stage.alloc(size_t(hi - lo)));
+      HIP_TRY(hipMemcpy(stage.as<void>(), reinterpret_cast<const void*>(lo), size_t(hi - lo), hipMemcpyHostToDevice));
     } else {  // separate arrays (SoA): two spans, the intensities' at a 256-byte boundary
       in_off = (long long)((p1 - p0 + 255) & ~uintptr_t(255));
-      e = hipMalloc(&d_stage, size_t(in_off) + size_t(q1 - q0));
-      if (e == hipSuccess) e = hipMemcpy(d_stage, points, size_t(p1 - p0), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMemcpy(d_stage + in_off, intensities, size_t(q1 - q0), hipMemcpyHostToDevice);
+      HIP_TRY(stage.alloc(size_t(in_off) + size_t(q1 - q0)));
+      HIP_TRY(hipMemcpy(stage.as<void>(), points, size_t(p1 - p0), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(stage.as<unsigned char>() + in_off, intensities, size_t(q1 - q0), hipMemcpyHostToDevice));
     }
-    if (e == hipSuccess) e = widen_cloud_device(d_stage, pt_off, point_stride, in_off, intensity_stride, num_points, c->d_pts, c->d_int, nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    HIP_TRY(widen_cloud_device(stage.as<void>(), pt_off, point_stride, in_off, intensity_stride, num_points, c->d_pts.as<double>(), c->d_int.as<double>(), nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(stage.reset());  // (a failed free of the staging buffer is reported like any other step)
   }
-  if (d_stage) {
-    const hipError_t ef = hipFree(d_stage);
-    if (e == hipSuccess) e = ef;
-  }
-  if (e != hipSuccess) {
-    if (c->d_pts) (void)hipFree(c->d_pts);
-    if (c->d_int) (void)hipFree(c->d_int);
-    delete c;
-    return fail(NIDREG_ERR_HIP, std::string("nidreg_cloud_create_f32: ") + hipGetErrorString(e));
-  }
-  *out = c;
+  *out = c.release();
   return NIDREG_OK;
 }
 
 void nidreg_cloud_destroy(nidreg_cloud* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  if (c->d_pts) (void)hipFree(c->d_pts);
-  if (c->d_int) (void)hipFree(c->d_int);
   delete c;
 }
 
@@ -496,42 +476,32 @@ int nidreg_project(nidreg_handle* h, const double* p3, int64_t n, double* uv, do
     // took, profiles/archive/r04q_profile_1bag_bfgs.txt).
     SmallProject& sp = g_small_project[h->device];
     std::lock_guard<std::mutex> lk(sp.mu);
-    if (!sp.host) {
-      void* blk = nullptr;
-      HIP_TRY(hipHostMalloc(&blk, size_t(kSmallProject) * 11 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+    if (!sp.dev) {
+      HIP_TRY(sp.block.alloc(size_t(kSmallProject) * 11 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
       void* dp = nullptr;
-      hipError_t e0 = hipHostGetDevicePointer(&dp, blk, 0);
-      if (e0 != hipSuccess) {
-        (void)hipHostFree(blk);
-        return fail(NIDREG_ERR_HIP, std::string("nidreg_project: ") + hipGetErrorString(e0));
-      }
-      sp.host = static_cast<double*>(blk);
+      HIP_TRY(hipHostGetDevicePointer(&dp, sp.block.as<void>(), 0));  // (on failure sp.dev stays null: the next call allocates again)
       sp.dev = static_cast<double*>(dp);
     }
-    std::memcpy(sp.host, p3, size_t(n) * 3 * sizeof(double));
+    double* const host = sp.block.as<double>();
+    std::memcpy(host, p3, size_t(n) * 3 * sizeof(double));
     double* d_uv = sp.dev + 3 * kSmallProject;
     double* d_j = jac ? sp.dev + 5 * kSmallProject : nullptr;
     hipError_t e = launch_project<double>(h->model, h->intr, h->dist, sp.dev, n, d_uv, d_j, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return fail(NIDREG_ERR_HIP, std::string("nidreg_project: ") + hipGetErrorString(e));
-    std::memcpy(uv, sp.host + 3 * kSmallProject, size_t(n) * 2 * sizeof(double));
-    if (jac) std::memcpy(jac, sp.host + 5 * kSmallProject, size_t(n) * 6 * sizeof(double));
+    std::memcpy(uv, host + 3 * kSmallProject, size_t(n) * 2 * sizeof(double));
+    if (jac) std::memcpy(jac, host + 5 * kSmallProject, size_t(n) * 6 * sizeof(double));
     return NIDREG_OK;
   }
-  double *d_p = nullptr, *d_uv = nullptr, *d_j = nullptr;
-  hipError_t e = hipMalloc(&d_p, size_t(n) * 3 * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&d_uv, size_t(n) * 2 * sizeof(double));
-  if (e == hipSuccess && jac) e = hipMalloc(&d_j, size_t(n) * 6 * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpy(d_p, p3, size_t(n) * 3 * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = launch_project<double>(h->model, h->intr, h->dist, d_p, n, d_uv, d_j, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e == hipSuccess) e = hipMemcpy(uv, d_uv, size_t(n) * 2 * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && jac) e = hipMemcpy(jac, d_j, size_t(n) * 6 * sizeof(double), hipMemcpyDeviceToHost);
-  if (d_p) (void)hipFree(d_p);
-  if (d_uv) (void)hipFree(d_uv);
-  if (d_j) (void)hipFree(d_j);
-  if (e != hipSuccess) return fail(NIDREG_ERR_HIP, std::string("nidreg_project: ") + hipGetErrorString(e));
+  DeviceBuf d_p, d_uv, d_j;
+  HIP_TRY(d_p.alloc(size_t(n) * 3 * sizeof(double)));
+  HIP_TRY(d_uv.alloc(size_t(n) * 2 * sizeof(double)));
+  if (jac) HIP_TRY(d_j.alloc(size_t(n) * 6 * sizeof(double)));
+  HIP_TRY(hipMemcpy(d_p.as<void>(), p3, size_t(n) * 3 * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(launch_project<double>(h->model, h->intr, h->dist, d_p.as<double>(), n, d_uv.as<double>(), d_j.as<double>(), h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(uv, d_uv.as<void>(), size_t(n) * 2 * sizeof(double), hipMemcpyDeviceToHost));
+  if (jac) HIP_TRY(hipMemcpy(jac, d_j.as<void>(), size_t(n) * 6 * sizeof(double), hipMemcpyDeviceToHost));
   return NIDREG_OK;
 }
 
@@ -629,8 +599,8 @@ int nidreg_project_model(int model_id, const double* intrinsics, const double* d
     std::memcpy(dist8, distortion, sizeof(dist8));
     return project_host(model_id, intr5, dist8, p3, n, uv, jac) == 0 ? NIDREG_OK : fail(NIDREG_ERR_INVALID, "nidreg_project_model: unknown camera model");
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(NIDREG_ERR_NO_DEVICE, "nidreg_project_model: no HIP device");
+  int ndev = 0;  // (the device id itself is checked by nidreg_project's hipSetDevice)
+  if (const int rc = count_devices("nidreg_project_model", &ndev)) return rc;
   nidreg_handle tmp;
   tmp.device = device_id;
   tmp.model = model_id;
@@ -646,33 +616,22 @@ int64_t nidreg_view_culling(int model_id, const double* intrinsics, const double
   if (model_id < 0 || model_id > 5 || !intrinsics || !distortion || width < 1 || height < 1 || num_points < 0 || !T_camera_lidar || (num_points > 0 && (!points || !indices_out)))
     return fail(NIDREG_ERR_INVALID, "nidreg_view_culling: bad argument");
   if (num_points == 0) return 0;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(NIDREG_ERR_NO_DEVICE, "nidreg_view_culling: no HIP device");
-  if (device_id < 0 || device_id >= ndev) return fail(NIDREG_ERR_INVALID, "nidreg_view_culling: device_id out of range");
-  HIP_TRY(hipSetDevice(device_id));
+  if (const int rc = use_device("nidreg_view_culling", device_id)) return rc;
   const int64_t stride = point_stride > 0 ? point_stride : 32;
   if (stride % 8 != 0 || stride < 32) return fail(NIDREG_ERR_INVALID, "nidreg_view_culling: point_stride must be a multiple of 8 and >= 32 ((x y z 1) doubles)");
-  double* d_pts = nullptr;
-  int* d_pix = nullptr;
-  unsigned int* d_zbuf = nullptr;
-  unsigned char* d_keep = nullptr;
+  DeviceBuf d_pts, d_pix, d_zbuf, d_keep;
   std::vector<unsigned char> keep(static_cast<size_t>(num_points));
-  hipError_t e = hipMalloc(&d_pts, size_t(num_points) * size_t(stride));
-  if (e == hipSuccess) e = hipMalloc(&d_pix, size_t(num_points) * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc(&d_zbuf, size_t(width) * height * sizeof(unsigned int));
-  if (e == hipSuccess) e = hipMalloc(&d_keep, size_t(num_points));
-  if (e == hipSuccess) e = hipMemcpy(d_pts, points, size_t(num_points) * size_t(stride), hipMemcpyHostToDevice);
+  HIP_TRY(d_pts.alloc(size_t(num_points) * size_t(stride)));
+  HIP_TRY(d_pix.alloc(size_t(num_points) * sizeof(int)));
+  HIP_TRY(d_zbuf.alloc(size_t(width) * height * sizeof(unsigned int)));
+  HIP_TRY(d_keep.alloc(size_t(num_points)));
+  HIP_TRY(hipMemcpy(d_pts.as<void>(), points, size_t(num_points) * size_t(stride), hipMemcpyHostToDevice));
   // CV_32FC1 filled with saturate_cast<float>(DBL_MAX) = +inf (view_culling.cpp:40) = 0x7f800000
-  if (e == hipSuccess) e = hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(d_zbuf), 0x7f800000, size_t(width) * height);
-  if (e == hipSuccess)
-    e = launch_cull(model_id, intrinsics, distortion, d_pts, stride / 8, num_points, T_camera_lidar, width, height, min_z, enable_depth_buffer_culling ? 1 : 0, d_pix, d_zbuf, d_keep, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(keep.data(), d_keep, size_t(num_points), hipMemcpyDeviceToHost);
-  if (d_pts) (void)hipFree(d_pts);
-  if (d_pix) (void)hipFree(d_pix);
-  if (d_zbuf) (void)hipFree(d_zbuf);
-  if (d_keep) (void)hipFree(d_keep);
-  if (e != hipSuccess) return fail(NIDREG_ERR_HIP, std::string("nidreg_view_culling: ") + hipGetErrorString(e));
+  HIP_TRY(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(d_zbuf.as<void>()), 0x7f800000, size_t(width) * height));
+  HIP_TRY(launch_cull(model_id, intrinsics, distortion, d_pts.as<double>(), stride / 8, num_points, T_camera_lidar, width, height, min_z, enable_depth_buffer_culling ? 1 : 0, d_pix.as<int>(),
+                      d_zbuf.as<unsigned int>(), d_keep.as<unsigned char>(), nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(keep.data(), d_keep.as<void>(), size_t(num_points), hipMemcpyDeviceToHost));
   int64_t m = 0;
   for (int64_t i = 0; i < num_points; i++)
     if (keep[size_t(i)]) indices_out[m++] = int32_t(i);
@@ -833,8 +792,8 @@ int nidreg_debug_round_chunks(int per_cu, int num_cus, const int64_t* gcount, in
 }
 
 void nidreg_trim(void) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess) return;
+  const int ndev = nidreg_device_count();
+  if (ndev <= 0) return;
   int cur = 0;
   (void)hipGetDevice(&cur);
   for (int dev = 0; dev < ndev && dev < 64; dev++) {

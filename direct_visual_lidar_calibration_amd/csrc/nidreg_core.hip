@@ -62,7 +62,7 @@ void unpool_host_block(int device, bool ring, void* p) {
   }
   (void)hipHostFree(p);
 }
-SmallProject g_small_project[NIDREG_MAX_DEVICES];
+SmallProject* const g_small_project = new SmallProject[NIDREG_MAX_DEVICES];
 
 void pool_release(int device) {
   std::vector<hipStream_t> streams;
@@ -78,38 +78,29 @@ void pool_release(int device) {
   for (void* b : blocks) (void)hipHostFree(b);
   SmallProject& sp = g_small_project[device];
   std::lock_guard<std::mutex> lk(sp.mu);
-  if (sp.host) (void)hipHostFree(sp.host);
-  sp.host = sp.dev = nullptr;
+  sp.block.reset();
+  sp.dev = nullptr;
 }
 
+// The teardown ORDER of a handle, all of it: everything that may still run kernels on the handle's memory goes first (the shard
+// set, the multi-pair groups, the cohort), then the handle's own stream is drained, and only then anything is released.  The
+// device memory is freed last, by the DeviceBuf members in `delete h`: with the handle's device current and its stream drained.
+// (Earlier versions freed the device memory before the pool returns.  After the synchronise the order of the two does not matter:
+// nothing of this handle runs, and a pooled stream or host block taken by another handle never touches this handle's memory.)
+// Nothing may be freed before the synchronise: a free that overtakes a running kernel faults the GPU.
 void free_handle(nidreg_handle* h) {
   if (!h) return;
   if (h->set) {
     free_shard_set(h->set);  // stops the workers and frees the other shards
     h->set = nullptr;
   }
-  drop_groups_of(h);
+  drop_groups_of(h);  // (a multi-pair group that evaluated this handle on its own stream is drained and freed there)
   cohort_leave(h);
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   rccl_release(h);
   for (auto& p : h->pending)  // tickets never collected: give their in-flight counts back to the device
     if (p.ticket != 0 && p.counted && h->device >= 0 && h->device < NIDREG_MAX_DEVICES) g_inflight[h->device].fetch_sub(1, std::memory_order_acq_rel);
-  if (h->d_pts) (void)hipFree(h->d_pts);
-  if (h->d_chunks) (void)hipFree(h->d_chunks);
-  if (h->d_chunks_hist) (void)hipFree(h->d_chunks_hist);
-  if (h->d_fused_scratch) (void)hipFree(h->d_fused_scratch);
-  if (h->d_eq_tab) (void)hipFree(h->d_eq_tab);
-  if (h->d_gend) (void)hipFree(h->d_gend);
-  if (h->d_img) (void)hipFree(h->d_img);
-  if (h->own_hist) {
-    if (h->d_hist_buf[0]) (void)hipFree(h->d_hist_buf[0]);
-    if (h->d_hist_buf[1]) (void)hipFree(h->d_hist_buf[1]);
-  }
-  if (h->d_shard_tab) (void)hipFree(h->d_shard_tab);
-  if (h->own_out && h->d_out) (void)hipFree(h->d_out);
-  if (h->d_scratch) (void)hipFree(h->d_scratch);
-  // (a multi-pair group that evaluated this handle on its own stream was drained and freed by drop_groups_of above)
   unpool_host_block(h->device, false, h->h_out);
   unpool_host_block(h->device, true, h->h_ring);
   for (int i = 0; i < 6; i++)
@@ -122,13 +113,13 @@ void fill_pass_args(const nidreg_handle* h, PassArgs& a) {
   std::memset(&a, 0, sizeof(a));
   a.model = h->model;
   a.rec64 = h->rec64;
-  a.pts = h->d_pts;
-  a.chunks = h->d_chunks;
+  a.pts = h->d_pts.as<void>();
+  a.chunks = h->d_chunks.as<Chunk>();
   a.nchunks = h->nchunks;
   a.nslots = h->nslots;
   a.seg = h->seg;
-  a.gend = h->d_gend;
-  a.img = h->d_img;
+  a.gend = h->d_gend.as<uint32_t>();
+  a.img = h->d_img.as<uint8_t>();
   a.pitch = h->pitch;
   a.W = h->W;
   a.H = h->H;
@@ -183,7 +174,7 @@ void pose_from_se3(const double* se3, double* R, double* t) {
 hipError_t begin_histogram(nidreg_handle* h, hipStream_t stream) {
   if (h->own_hist) {
     h->hist_cur ^= 1;
-    h->d_hist = h->d_hist_buf[h->hist_cur];
+    h->d_hist = h->d_hist_buf[h->hist_cur].as<u64>();
     // The buffer was cleared by the PREVIOUS evaluation's kernels (plain stores of k_entropy / the gradient prologue), and the
     // host may be here before that kernel has ended: it proceeds on the completion tag.  On the same stream the kernel boundary
     // orders the clears against this evaluation's atomics; on another stream (a cohort round on a different group's stream, a
@@ -209,7 +200,7 @@ int launch_hist_spline(nidreg_handle* h, const double* se3, bool alone) {
   fill_pass_args(h, a);
   a.prio = alone ? 1 : 0;
   if (h->d_chunks_hist) {
-    a.chunks = h->d_chunks_hist;
+    a.chunks = h->d_chunks_hist.as<Chunk>();
     a.nchunks = h->nchunks_hist;
     a.seg = h->seg_hist;
   }
@@ -290,8 +281,8 @@ NearestFastArgs nearest_fast_args(const nidreg_handle* h, const double* T) {
   } else if (h->model == NIDREG_MODEL_EQUIRECTANGULAR) {
     // round 6: decided on the pixel boundaries (nid_kernels.hpp below NearestFast): the tables built at creation, bands per point
     if (!h->d_eq_tab) return f;
-    f.tab_c = h->d_eq_tab;
-    f.tab_r = h->d_eq_tab + 2 * size_t(h->eq_kmax + 1);
+    f.tab_c = h->d_eq_tab.as<double>();
+    f.tab_r = f.tab_c + 2 * size_t(h->eq_kmax + 1);
     f.kmax = h->eq_kmax;
     f.jmax = h->eq_jmax;
   } else {
@@ -319,7 +310,7 @@ int launch_entropy(nidreg_handle* h, double tag, bool tail) {
   const double inv_unit = 1.0 / fixed_unit(h);
   hipLaunchKernelGGL(
     k_entropy<false>, dim3(h->NEB), dim3(kEntropyThreads), 0, h->stream, h->d_hist, h->bins, kEntropyCols, inv_unit, h->d_part_hj, h->d_row_part, h->d_phi_q, h->d_hist_image,
-    h->d_hist_points, h->d_scal, h->d_out, h->d_out_host, tag, h->d_counters, h->own_hist ? h->d_hist_buf[h->hist_cur ^ 1] : nullptr, h->hist_words, tail ? 1 : 0,
+    h->d_hist_points, h->d_scal, h->d_out, h->d_out_host, tag, h->d_counters, h->own_hist ? h->d_hist_buf[h->hist_cur ^ 1].as<u64>() : nullptr, h->hist_words, tail ? 1 : 0,
     static_cast<const MultiEntry*>(nullptr), NoMultiDyn());
   HIP_TRY(hipGetLastError());
   if (h->own_hist) {
@@ -352,7 +343,7 @@ int launch_grad(nidreg_handle* h, bool alone, int from_partials) {
   a.prio = alone ? 1 : 0;
   a.gt_from_partials = from_partials;
   if (from_partials == 2) {
-    a.gt_zero_buf = h->own_hist ? h->d_hist_buf[h->hist_cur ^ 1] : nullptr;
+    a.gt_zero_buf = h->own_hist ? h->d_hist_buf[h->hist_cur ^ 1].as<u64>() : nullptr;
     a.gt_zero_words = h->hist_words;
     if (h->own_hist) {
       h->hist_zeroed[h->hist_cur ^ 1] = true;  // zeroed by this evaluation's gradient kernel for the next one
@@ -431,10 +422,10 @@ void plan_fused(nidreg_handle* h) {
     const int occ = occupancy_spline_fused(a, fa);
     if (occ <= 0 || int64_t(occ) * h->num_cus < int64_t(h->nchunks)) continue;
     const size_t sbytes = 256 + size_t(h->nchunks) * 128;  // the arrival counter, then one release word per workgroup in a line of its own
-    if (hipMalloc(&h->d_fused_scratch, sbytes) != hipSuccess) return;
-    if (hipMemset(h->d_fused_scratch, 0, sbytes) != hipSuccess) return;
+    if (h->d_fused_scratch.alloc(sbytes) != hipSuccess) return;
+    if (hipMemset(h->d_fused_scratch.as<void>(), 0, sbytes) != hipSuccess) return;
     if (hipDeviceSynchronize() != hipSuccess) return;  // (the null-stream memset against the handle's non-blocking stream)
-    h->d_fused_barrier = static_cast<u64*>(h->d_fused_scratch);
+    h->d_fused_barrier = h->d_fused_scratch.as<u64>();
     h->fused_launches = 0;
     h->fused_cap = cap;
     h->fused_full = f;
@@ -455,7 +446,6 @@ bool fused_usable(nidreg_handle* h) {
 // handle, its counters are cleared (workgroups that gave up never drew their tickets)
 void fused_give_up(nidreg_handle* h) {
   h->fused = -1;
-  h->fused_last = false;
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
   (void)hipMemsetAsync(h->d_counters, 0, 8 * sizeof(unsigned int), h->stream);
@@ -473,7 +463,7 @@ int eval_launch_fused(nidreg_handle* h, const double* se3) {
   fill_pass_args(h, a);  // (after begin_histogram: a.hist = this evaluation's buffer; a.q = the pose's quaternion; a.tag = its sequence number)
   std::memcpy(a.R, h->last_R, sizeof(a.R));
   std::memcpy(a.t, h->last_t, sizeof(a.t));
-  a.gt_zero_buf = h->d_hist_buf[h->hist_cur ^ 1];
+  a.gt_zero_buf = h->d_hist_buf[h->hist_cur ^ 1].as<u64>();
   a.gt_zero_words = h->hist_words;
   h->hist_zeroed[h->hist_cur ^ 1] = true;  // cleared by this launch for the next evaluation
   h->zero_stream = h->stream;
@@ -488,12 +478,10 @@ int eval_launch_fused(nidreg_handle* h, const double* se3) {
   HIP_TRY(launch_spline_fused(a, f));
   if (h->timing) HIP_TRY(hipEventRecord(h->ev[5], h->stream));
   h->ev_grad = true;
-  h->fused_last = true;
   return NIDREG_OK;
 }
 
 int eval_launch(nidreg_handle* h, const double* se3, bool want_grad, bool alone) {
-  h->fused_last = false;
   const int rc = eval_launch_first(h, se3, alone);
   if (rc) return rc;
   return eval_launch_rest(h, want_grad, alone);

@@ -55,19 +55,11 @@ static_assert(int(ncclSuccess) == 0 && int(ncclSum) == 0 && int(ncclMax) == 2 &&
 }  // namespace rccl_header_check
 #endif
 
-#include "../../include/nidreg.h"
-
 using namespace nidreg;
 
 extern thread_local std::string g_last_error;  // nidreg_last_error() of the calling thread (nidreg_core.hip; set by nidreg::fail)
 
 namespace {
-
-#define HIP_TRY(expr)                                                                                   \
-  do {                                                                                                  \
-    hipError_t _e = (expr);                                                                             \
-    if (_e != hipSuccess) return fail(NIDREG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 // double -> int exactly as the reference's x86-64 build converts (cvttsd2si): NaN / overflow -> INT_MIN
 inline int cast_int(double d) {
@@ -113,18 +105,28 @@ struct nidreg_handle {
   hipStream_t stream = nullptr;
   bool own_stream = false;
   hipStream_t last_stream = nullptr;  // the stream the most recent evaluation's kernels ran on (a multi-pair group's, else `stream`): what the histogram getters drain
-  void* d_pts = nullptr;
-  Chunk* d_chunks = nullptr;
-  Chunk* d_chunks_hist = nullptr;
-  uint32_t* d_gend = nullptr;  // [NG] end offsets of the column groups among the records (nid_kernels.hpp Segments)
-  uint8_t* d_img = nullptr;
+  // Device memory: these DeviceBuf members own their allocation and free it when free_handle deletes the handle.  Members
+  // are destroyed last to first, so they are declared in the REVERSE of the order the allocator gets them back in -- records
+  // first, scratch last, the order handles have always been freed in (about the order they were allocated in).  The plain
+  // pointers further down (d_hist, d_out, d_part_hj ... d_counters, d_fused_barrier) are what the kernels are handed: views into
+  // an owner or a caller's buffer (desc.ext_hist / ext_out), filled at creation.
+  DeviceBuf d_scratch;        // ONE allocation carved into the per-evaluation scratch below (zeroed at creation)
+  DeviceBuf d_out_buf;        // double[NIDREG_OUT_DOUBLES] behind d_out (own_out)
+  DeviceBuf d_shard_tab;      // device copy of this shard's ShardTable (peer flag / gather blocks, owned columns)
+  DeviceBuf d_hist_buf[2];    // u64[hist_words] each: the histogram double buffer (own_hist)
+  DeviceBuf d_img;            // uint8_t padded bin image
+  DeviceBuf d_gend;           // uint32_t[NG] end offsets of the column groups among the records (nid_kernels.hpp Segments)
+  DeviceBuf d_eq_tab;         // double[2 (eq_kmax + 1) + eq_jmax + 1]: NEAREST, equirectangular (below)
+  DeviceBuf d_fused_scratch;  // the grid barrier's arrival counter (256 B), then its per-workgroup release words (128 B each)
+  DeviceBuf d_chunks_hist;    // Chunk[chunks_hist_cap]
+  DeviceBuf d_chunks;         // Chunk[chunks_cap]
+  DeviceBuf d_pts;            // Rec64 / Rec32 records
   u64* d_hist = nullptr;      // histogram of the current / most recent evaluation (accumulation target of pass A)
   // a shard of a ShardSet owns a range of histogram COLUMN GROUPS: it holds the points of those columns only, and its
   // histogram is the pair's histogram restricted to them (the other columns stay zero)
   struct ShardSet* set = nullptr;  // non-NULL on the leader (shard 0) of a set: nidreg_eval* fan out over the shards
   bool is_shard = false;
   int shard_index = 0;
-  ShardTable* d_shard_tab = nullptr;  // device copy of this shard's ShardTable (peer flag / gather blocks, owned columns)
   // one process per GPU (nidreg_shard_attach_rccl / nidreg_shard_comm_init): this handle holds an index-range slice of the pair,
   // every evaluation all-reduces the integer histogram (and the 7-double gradient partial) over this communicator
   void* rccl_comm = nullptr;
@@ -133,14 +135,12 @@ struct nidreg_handle {
   size_t img_bytes = 0;
   // double buffering of the histogram (own buffers only): evaluation k accumulates into one buffer and
   // its k_entropy zeroes the OTHER one for evaluation k + 1, so no memset sits on the critical path
-  u64* d_hist_buf[2] = {nullptr, nullptr};
   bool hist_zeroed[2] = {false, false};
   hipStream_t zero_stream = nullptr;  // the stream of the kernel that cleared the idle buffer (begin_histogram orders a launch on another stream behind it)
   int hist_cur = 0;
-  bool own_hist = false;
+  bool own_hist = false;  // d_hist alternates between d_hist_buf[0 / 1] (else: the caller's ext_hist)
   double* d_out = nullptr;
-  bool own_out = false;
-  void* d_scratch = nullptr;  // ONE allocation carved into the per-evaluation scratch below (zeroed at creation)
+  bool own_out = false;  // d_out is d_out_buf (else: the caller's ext_out)
   long long* d_part_hj = nullptr;  // fixed-point entropy partials (nid_kernels.hpp ent_fixed)
   u64* d_row_part = nullptr;
   double* d_phi_q = nullptr;
@@ -178,15 +178,12 @@ struct nidreg_handle {
   int fused = 0;               // 0: not planned yet, 1: usable, -1: not applicable / switched off (a barrier that timed out)
   int fused_cap = 0, fused_full = 0; // points of LDS stash per workgroup; 1: full stash format, 0: (u, v) only
   int64_t longest_chunk = 0;         // records of the longest chunk of the gradient-pass table (0: unknown -> no fused route)
-  void* d_fused_scratch = nullptr;   // the grid barrier's arrival counter (256 B), then its per-workgroup release words (128 B each)
   u64* d_fused_barrier = nullptr;
   uint64_t fused_arrivals = 0;       // arrivals the counter holds once every launch so far has passed its barrier
   uint64_t fused_launches = 0;       // fused launches so far (the barrier's epoch)
-  bool fused_last = false;           // the evaluation in flight (or last finished) ran on the fused route
 
   // NEAREST, equirectangular: (cos, sin) of the column-boundary longitudes, then the signed squared sines of the row-boundary
-  // latitudes (nid_kernels.hpp NearestFast); eq_kmax / eq_jmax = ceil of the intrinsics' W / H
-  double* d_eq_tab = nullptr;
+  // latitudes (nid_kernels.hpp NearestFast) in d_eq_tab; eq_kmax / eq_jmax = ceil of the intrinsics' W / H
   int eq_kmax = 0, eq_jmax = 0;
 
   int timing = 0;  // 1: per-kernel events (three-kernel path), 2: events around whichever path runs
@@ -229,8 +226,9 @@ struct Cohort {
 // go unnoticed).
 struct ShardSet {
   std::vector<nidreg_handle*> shards;  // [0] = the leader (owns this set), the rest are owned by the set
-  std::vector<u64*> flags;             // per shard: fine-grained flag block on its device (kFlagWords)
-  std::vector<u64*> gather;            // per shard: fine-grained gather block (kGatherWords)
+  // (flags and gather have the length of shards from the moment the set exists: free_shard_set indexes them by shard)
+  std::vector<DeviceBuf> flags;        // per shard: fine-grained flag block on its device (kFlagWords)
+  std::vector<DeviceBuf> gather;       // per shard: fine-grained gather block (kGatherWords)
   int CB = kEntropyCols, nblocks = 0;  // k_entropy_repl: columns per workgroup, workgroups (every cut between shards is a multiple of CB columns)
   std::vector<int> lock_devices;       // distinct devices of the set, ascending: set_eval locks them in this order
   bool colocated = false;              // a device is listed more than once (a 1-GPU box exercising the protocol)
@@ -258,8 +256,8 @@ struct ShardSet {
 struct nidreg_cloud {
   int device = 0;
   int64_t n = 0;
-  double* d_pts = nullptr;  // n x 4 doubles (x y z 1)
-  double* d_int = nullptr;  // n doubles
+  DeviceBuf d_pts;  // n x 4 doubles (x y z 1)
+  DeviceBuf d_int;  // n doubles
 };
 
 // ---- everything below: declarations shared by the translation units of libnidreg.so's host side (nidreg_core / _plan / _multi / _rccl / _shard / _abi .hip)
@@ -285,10 +283,10 @@ constexpr size_t kPoolCap = 64;
 constexpr int64_t kSmallProject = 64;
 struct SmallProject {
   std::mutex mu;
-  double* host = nullptr;
-  double* dev = nullptr;
+  HostBuf block;
+  double* dev = nullptr;  // device address of `block` (nullptr: not allocated yet)
 };
-extern SmallProject g_small_project[NIDREG_MAX_DEVICES];
+extern SmallProject* const g_small_project;  // [NIDREG_MAX_DEVICES]; never destroyed: a HostBuf must not call HIP from a static destructor at process exit
 
 // Evaluations in flight per device (this process).  An evaluation that has its device to itself runs with progress
 // priority in the spline passes; with several callers on one GPU (the reference's OpenMP loop over pairs,
@@ -344,9 +342,9 @@ struct MultiGroup {
   std::vector<nidreg_handle*> hs;
   int device = 0;
   hipStream_t stream = nullptr;
-  MultiEntry* d_table = nullptr;
-  Chunk* d_chunks = nullptr;       // gradient pass / generic histogram kernels
-  Chunk* d_chunks_hist = nullptr;  // WIDE histogram kernel
+  DeviceBuf d_table;        // MultiEntry[hs.size()]
+  DeviceBuf d_chunks;       // Chunk[]: gradient pass / generic histogram kernels
+  DeviceBuf d_chunks_hist;  // Chunk[]: WIDE histogram kernel
   int seg = 0, seg_hist = 0;       // the combined tables have chunks that run across column groups (SEG kernels)
   size_t lds_grad = 0;
   int nchunks = 0, nchunks_hist = 0;

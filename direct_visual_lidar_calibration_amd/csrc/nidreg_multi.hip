@@ -16,11 +16,8 @@ void free_group(MultiGroup* g) {
     if (m->last_stream == g->stream) m->last_stream = m->stream;
     if (m->zero_stream == g->stream) m->zero_stream = nullptr;  // drained above: nothing left to order against
   }
-  if (g->d_table) (void)hipFree(g->d_table);
-  if (g->d_chunks) (void)hipFree(g->d_chunks);
-  if (g->d_chunks_hist) (void)hipFree(g->d_chunks_hist);
   if (g->stream) unpool_stream(g->device, g->stream);  // (synchronised above)
-  delete g;
+  delete g;  // (frees the tables last, device current and stream drained: the order free_handle's header explains)
 }
 // called by free_handle: a group dies with any of its members
 void drop_groups_of(const nidreg_handle* h) {
@@ -90,15 +87,14 @@ int cohort_reshape(nidreg_handle* h, int64_t total_points) {
     const int64_t share = std::max<int64_t>(1, round_chunks(per_cu, h->num_cus, total_points) * mine / total_points);
     return split_groups(h->gcount.data(), h->NG, share, segment_overhead(wide_hist), max_segments(h->mode, h->GW), -1, chunks);
   };
-  auto upload = [&](const std::vector<Chunk>& chunks, Chunk*& d_tab, size_t& cap) -> int {
+  auto upload = [&](const std::vector<Chunk>& chunks, DeviceBuf& d_tab, size_t& cap) -> int {
     if (chunks.size() > cap) {
-      Chunk* fresh = nullptr;
-      HIP_TRY(hipMalloc(&fresh, chunks.size() * sizeof(Chunk)));
-      if (d_tab) (void)hipFree(d_tab);
-      d_tab = fresh;
+      DeviceBuf fresh;
+      HIP_TRY(fresh.alloc(chunks.size() * sizeof(Chunk)));
+      d_tab = std::move(fresh);  // (the old table is freed after the new one exists: a failed allocation leaves it in place)
       cap = chunks.size();
     }
-    if (!chunks.empty()) HIP_TRY(hipMemcpy(d_tab, chunks.data(), chunks.size() * sizeof(Chunk), hipMemcpyHostToDevice));
+    if (!chunks.empty()) HIP_TRY(hipMemcpy(d_tab.as<void>(), chunks.data(), chunks.size() * sizeof(Chunk), hipMemcpyHostToDevice));
     return NIDREG_OK;
   };
   std::vector<Chunk> grad_chunks, hist_chunks;
@@ -240,11 +236,11 @@ MultiGroup* find_or_make_group(nidreg_handle* const* handles, int n) {
       }
     }
     MultiEntry& e = table[size_t(i)];
-    e.pts = h->d_pts;
-    e.gend = h->d_gend;
-    e.img = h->d_img;
-    e.hist_buf[0] = h->d_hist_buf[0];
-    e.hist_buf[1] = h->d_hist_buf[1];
+    e.pts = h->d_pts.as<void>();
+    e.gend = h->d_gend.as<uint32_t>();
+    e.img = h->d_img.as<uint8_t>();
+    e.hist_buf[0] = h->d_hist_buf[0].as<u64>();
+    e.hist_buf[1] = h->d_hist_buf[1].as<u64>();
     e.k16 = fixed_unit_k(h);
     e.inv_unit = 1.0 / fixed_unit(h);
     e.part_hj = h->d_part_hj;
@@ -275,13 +271,13 @@ MultiGroup* find_or_make_group(nidreg_handle* const* handles, int n) {
   for (int i = 0; i < n; i++) wide_chunks.insert(wide_chunks.end(), pair_hist[size_t(i)].begin(), pair_hist[size_t(i)].end());
   hipError_t err = hipSetDevice(g->device);
   if (err == hipSuccess) err = pool_stream(g->device, &g->stream);
-  if (err == hipSuccess) err = hipMalloc(&g->d_table, table.size() * sizeof(MultiEntry));
-  if (err == hipSuccess) err = hipMemcpy(g->d_table, table.data(), table.size() * sizeof(MultiEntry), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMalloc(&g->d_chunks, std::max<size_t>(chunks.size(), 1) * sizeof(Chunk));
-  if (err == hipSuccess && !chunks.empty()) err = hipMemcpy(g->d_chunks, chunks.data(), chunks.size() * sizeof(Chunk), hipMemcpyHostToDevice);
+  if (err == hipSuccess) err = g->d_table.alloc(table.size() * sizeof(MultiEntry));
+  if (err == hipSuccess) err = hipMemcpy(g->d_table.as<void>(), table.data(), table.size() * sizeof(MultiEntry), hipMemcpyHostToDevice);
+  if (err == hipSuccess) err = g->d_chunks.alloc(std::max<size_t>(chunks.size(), 1) * sizeof(Chunk));
+  if (err == hipSuccess && !chunks.empty()) err = hipMemcpy(g->d_chunks.as<void>(), chunks.data(), chunks.size() * sizeof(Chunk), hipMemcpyHostToDevice);
   if (err == hipSuccess && h0->wide) {
-    err = hipMalloc(&g->d_chunks_hist, std::max<size_t>(wide_chunks.size(), 1) * sizeof(Chunk));
-    if (err == hipSuccess && !wide_chunks.empty()) err = hipMemcpy(g->d_chunks_hist, wide_chunks.data(), wide_chunks.size() * sizeof(Chunk), hipMemcpyHostToDevice);
+    err = g->d_chunks_hist.alloc(std::max<size_t>(wide_chunks.size(), 1) * sizeof(Chunk));
+    if (err == hipSuccess && !wide_chunks.empty()) err = hipMemcpy(g->d_chunks_hist.as<void>(), wide_chunks.data(), wide_chunks.size() * sizeof(Chunk), hipMemcpyHostToDevice);
   }
   if (err != hipSuccess) {
     evicted.push_back(g);  // (freed once the lock is released)
@@ -313,7 +309,7 @@ int group_eval(MultiGroup* g, const double* se3, bool want_grad, double* costs, 
   PassArgs a;
   fill_pass_args(h0, a);
   a.stream = g->stream;
-  a.multi = g->d_table;
+  a.multi = g->d_table.as<MultiEntry>();
   a.dyn.want_grad = want_grad ? 1 : 0;
   a.dyn.neb = h0->NEB;
   InflightGuard guard(g->device);
@@ -333,7 +329,7 @@ int group_eval(MultiGroup* g, const double* se3, bool want_grad, double* costs, 
     h->ev_grad = want_grad;
     }
   // pass A
-  a.chunks = h0->wide ? g->d_chunks_hist : g->d_chunks;
+  a.chunks = (h0->wide ? g->d_chunks_hist : g->d_chunks).as<Chunk>();
   a.nchunks = h0->wide ? g->nchunks_hist : g->nchunks;
   a.seg = h0->wide ? g->seg_hist : g->seg;
   HIP_TRY(launch_spline_hist<double>(a));
@@ -345,7 +341,7 @@ int group_eval(MultiGroup* g, const double* se3, bool want_grad, double* costs, 
     hipLaunchKernelGGL(
       k_entropy<true>, dim3(h0->NEB * n), dim3(kEntropyThreads), 0, g->stream, static_cast<u64*>(nullptr), h0->bins, kEntropyCols, 0.0, static_cast<long long*>(nullptr),
       static_cast<u64*>(nullptr), static_cast<double*>(nullptr), static_cast<double*>(nullptr), static_cast<double*>(nullptr), static_cast<EntropyScalars*>(nullptr), static_cast<double*>(nullptr),
-      static_cast<double*>(nullptr), 0.0, static_cast<unsigned int*>(nullptr), static_cast<u64*>(nullptr), 0ll, 1, static_cast<const MultiEntry*>(g->d_table), a.dyn);
+      static_cast<double*>(nullptr), 0.0, static_cast<unsigned int*>(nullptr), static_cast<u64*>(nullptr), 0ll, 1, g->d_table.as<const MultiEntry>(), a.dyn);
     HIP_TRY(hipGetLastError());
   }
   for (int i = 0; i < n; i++) {
@@ -354,7 +350,7 @@ int group_eval(MultiGroup* g, const double* se3, bool want_grad, double* costs, 
   }
   // pass B (k_entropy<true> ran without its tail for every pair that has gradient workgroups: they run it)
   if (want_grad) {
-    a.chunks = g->d_chunks;
+    a.chunks = g->d_chunks.as<Chunk>();
     a.nchunks = g->nchunks;
     a.seg = g->seg;
     a.lds_grad = g->lds_grad;
@@ -377,7 +373,7 @@ int group_eval(MultiGroup* g, const double* se3, bool want_grad, double* costs, 
         unsigned int c[8];
         (void)hipMemcpy(c, hj->d_counters, sizeof(c), hipMemcpyDeviceToHost);
         std::vector<MultiEntry> tab(static_cast<size_t>(n));
-        (void)hipMemcpy(tab.data(), g->d_table, tab.size() * sizeof(MultiEntry), hipMemcpyDeviceToHost);
+        (void)hipMemcpy(tab.data(), g->d_table.as<void>(), tab.size() * sizeof(MultiEntry), hipMemcpyDeviceToHost);
         std::fprintf(stderr, "group debug: pair %d seq %.0f tag %.0f cost %.6f counters %u %u %u %u nchunks(table) %d group nchunks %d/%d\n", j, hj->seq, hj->h_out[15], hj->h_out[0], c[0], c[1], c[2], c[3],
                      tab[size_t(j)].nchunks, g->nchunks, g->nchunks_hist);
       }
@@ -518,7 +514,7 @@ int group_eval_iso(MultiGroup* g, const double* T, double* costs) {
   PassArgs a;
   fill_pass_args(h0, a);
   a.stream = g->stream;
-  a.multi = g->d_table;
+  a.multi = g->d_table.as<MultiEntry>();
   a.dyn.want_grad = 0;
   a.dyn.neb = h0->NEB;
   for (int k = 0; k < 12; k++) a.iso[k] = T[k];
@@ -532,14 +528,14 @@ int group_eval_iso(MultiGroup* g, const double* T, double* costs) {
     h->last_stream = g->stream;
     h->ev_grad = false;
   }
-  a.chunks = g->d_chunks;
+  a.chunks = g->d_chunks.as<Chunk>();
   a.nchunks = g->nchunks;
   a.seg = g->seg;
   HIP_TRY(launch_nearest_hist<double>(a));
   hipLaunchKernelGGL(
     k_entropy<true>, dim3(h0->NEB * n), dim3(kEntropyThreads), 0, g->stream, static_cast<u64*>(nullptr), h0->bins, kEntropyCols, 0.0, static_cast<long long*>(nullptr),
     static_cast<u64*>(nullptr), static_cast<double*>(nullptr), static_cast<double*>(nullptr), static_cast<double*>(nullptr), static_cast<EntropyScalars*>(nullptr), static_cast<double*>(nullptr),
-    static_cast<double*>(nullptr), 0.0, static_cast<unsigned int*>(nullptr), static_cast<u64*>(nullptr), 0ll, 1, static_cast<const MultiEntry*>(g->d_table), a.dyn);
+    static_cast<double*>(nullptr), 0.0, static_cast<unsigned int*>(nullptr), static_cast<u64*>(nullptr), 0ll, 1, g->d_table.as<const MultiEntry>(), a.dyn);
   HIP_TRY(hipGetLastError());
   for (int i = 0; i < n; i++) {
     g->hs[size_t(i)]->hist_zeroed[g->hs[size_t(i)]->hist_cur ^ 1] = true;

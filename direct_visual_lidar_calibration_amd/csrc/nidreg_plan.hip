@@ -198,7 +198,7 @@ int resolve_wide_bins(const nidreg_desc* d, const nidreg_cloud* cloud, WideBins&
   }
   if (cloud) {
     HIP_TRY(hipSetDevice(cloud->device));
-    HIP_TRY(mark_bins_device(cloud->d_int, cloud->n, B, used_pts.data()));
+    HIP_TRY(mark_bins_device(cloud->d_int.as<double>(), cloud->n, B, used_pts.data()));
   } else {
     for (int64_t i = 0; i < d->num_points; i++) used_pts[size_t(std::max(0, std::min(B - 1, cast_int(d->intensities[i] * double(B)))))] = 1;  // nid_cost.hpp:49
   }
@@ -225,9 +225,18 @@ int resolve_wide_bins(const nidreg_desc* d, const nidreg_cloud* cloud, WideBins&
   return NIDREG_OK;
 }
 
-int create_impl(const nidreg_desc* d, const nidreg_cloud* cloud, const double* T_cull, double min_z, int enable_depth, const CreateOpts& opts, nidreg_handle** out) {
-  if (!d || !out) return fail(NIDREG_ERR_INVALID, "nidreg_create: null argument");
-  *out = nullptr;
+// ---- handle construction: create_impl below runs these stages in this order.  Everything is built ON THE DEVICE from one upload
+// of the caller's arrays (the reference constructs a cost object per pair per outer iteration,
+// visual_camera_calibration.cpp:199-208, so construction time counts).  A stage that fails returns the error; the handle under
+// construction is then freed by its owner in create_impl (free_handle).
+namespace {
+
+inline int image_strips(int H) { return (H + 3 + 3) / 4 + 1; }  // padded rows are stored in strips of four (nid_device.hpp load_patch)
+
+// Every argument check that comes before the device is selected; nothing is allocated.  Out: dd = the desc the later stages
+// read (bins = the compact count when bins > 256), wide = the compact layout (or null), n_in = points that go in.
+// (bins > 256 over a device-resident cloud marks the occupied bins on the cloud's GPU: resolve_wide_bins)
+int check_desc(const nidreg_desc* d, const nidreg_cloud* cloud, const CreateOpts& opts, nidreg_desc& dd, WideBins& wide_here, const WideBins*& wide, int64_t& n_in) {
   if (d->struct_size != int32_t(sizeof(nidreg_desc))) return fail(NIDREG_ERR_INVALID, "nidreg_create: struct_size mismatch");
   if (d->model_id < 0 || d->model_id > 5) return fail(NIDREG_ERR_INVALID, "nidreg_create: unknown camera model");
   // The reference takes any int (src/calibrate.cpp:175 --nid_bins, nid_cost.hpp:23); its own data path quantises BOTH inputs
@@ -240,9 +249,8 @@ int create_impl(const nidreg_desc* d, const nidreg_cloud* cloud, const double* T
   const nidreg_handle* master = opts.shard ? opts.master : nullptr;
   if (opts.shard && !master) return fail(NIDREG_ERR_INVALID, "nidreg_create: shard without a master");
   // bins > 256: run on the occupied bins, compacted (WideBins above); a shard takes its master's compact layout
-  WideBins wide_here;
-  const WideBins* wide = opts.wide;
-  nidreg_desc dd;
+  dd = *d;
+  wide = opts.wide;
   if (!opts.shard && d->bins > NIDREG_MAX_BINS) {
     if (!wide) {
       if (d->image_dtype != NIDREG_IMAGE_F64 && d->image_dtype != NIDREG_IMAGE_U8) return fail(NIDREG_ERR_INVALID, "nidreg_create: bad image_dtype");
@@ -251,13 +259,11 @@ int create_impl(const nidreg_desc* d, const nidreg_cloud* cloud, const double* T
       if (rc) return rc;
       wide = &wide_here;
     }
-    dd = *d;
     dd.bins = wide->compact_bins;
-    d = &dd;
   } else if (opts.shard && d->bins > NIDREG_MAX_BINS) {
     return fail(NIDREG_ERR_INVALID, "nidreg_create: a shard is created with its master's compact bin count");
   }
-  const int64_t n_in = master ? master->gcount[size_t(opts.group_hi)] - master->gcount[size_t(opts.group_lo)] : (cloud ? cloud->n : d->num_points);
+  n_in = master ? master->gcount[size_t(opts.group_hi)] - master->gcount[size_t(opts.group_lo)] : (cloud ? cloud->n : d->num_points);
   if (n_in < 0 || n_in > int64_t(INT_MAX)) return fail(NIDREG_ERR_INVALID, "nidreg_create: bad num_points");
   if (!master && !cloud && n_in > 0 && (!d->points || !d->intensities)) return fail(NIDREG_ERR_INVALID, "nidreg_create: null points");
   if (cloud && cloud->device != d->device_id) return fail(NIDREG_ERR_INVALID, "nidreg_create_from_cloud: cloud lives on another device");
@@ -266,19 +272,27 @@ int create_impl(const nidreg_desc* d, const nidreg_cloud* cloud, const double* T
   // |dNID| <= 2e-5; a mode that cheap to lose was not worth its kernel instantiations and was removed rather than kept half-built)
   if (d->precision != NIDREG_PREC_FP64)
     return fail(NIDREG_ERR_INVALID, d->precision == NIDREG_PREC_FP32 ? "nidreg_create: NIDREG_PREC_FP32 was removed (it bought 8 %); the core computes in double" : "nidreg_create: bad precision");
+  return NIDREG_OK;
+}
+// ... and the three that have always come AFTER the device selection: on a machine without a GPU a bad image_dtype or stride
+// reports the missing device, and keeps doing so
+int check_after_device(const nidreg_desc& d, const nidreg_cloud* cloud, int64_t n_in) {
+  if (d.image_dtype != NIDREG_IMAGE_F64 && d.image_dtype != NIDREG_IMAGE_U8) return fail(NIDREG_ERR_INVALID, "nidreg_create: bad image_dtype");
+  if (d.image_row_stride < int64_t(d.width) * (d.image_dtype == NIDREG_IMAGE_F64 ? 8 : 1)) return fail(NIDREG_ERR_INVALID, "nidreg_create: image_row_stride smaller than a row");
+  const int64_t pstride = d.point_stride > 0 ? d.point_stride : 32;
+  if (!cloud && n_in > 0 && (pstride < 32 || pstride % 8 != 0)) return fail(NIDREG_ERR_INVALID, "nidreg_create: point_stride must be a multiple of 8 and >= 32 ((x y z 1) doubles)");
+  return NIDREG_OK;
+}
 
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(NIDREG_ERR_NO_DEVICE, "nidreg_create: no HIP device (the NID core has no CPU path)");
-  if (d->device_id < 0 || d->device_id >= ndev) return fail(NIDREG_ERR_INVALID, "nidreg_create: device_id out of range");
-  HIP_TRY(hipSetDevice(d->device_id));
-
-  nidreg_handle* h = new nidreg_handle();
-  h->device = d->device_id;
-  h->model = d->model_id;
-  h->mode = d->mode;
-  h->precision = d->precision;
-  h->bins = d->bins;
-  h->nearest_exact = (d->flags & NIDREG_FLAG_NEAREST_EXACT) != 0;
+// The handle's host-side description: what the caller asked for, the tiling, the LDS sizes, the fixed-point unit and the
+// layout of the padded bin image.  Pure arithmetic.
+void plan_tiling(nidreg_handle* h, const nidreg_desc& d, const WideBins* wide, const nidreg_handle* master, int64_t n_in) {
+  h->device = d.device_id;
+  h->model = d.model_id;
+  h->mode = d.mode;
+  h->precision = d.precision;
+  h->bins = d.bins;
+  h->nearest_exact = (d.flags & NIDREG_FLAG_NEAREST_EXACT) != 0;
   if (wide) {
     h->bins_user = wide->user_bins;
     h->inv_img = wide->inv_img;
@@ -288,29 +302,19 @@ int create_impl(const nidreg_desc* d, const nidreg_cloud* cloud, const double* T
     h->inv_img = master->inv_img;
     h->inv_pts = master->inv_pts;
   }
-  h->W = d->width;
-  h->H = d->height;
-  h->num_points = n_in;
-  h->max_fov = d->max_fov;
-  std::memcpy(h->intr, d->intrinsics, sizeof(h->intr));
-  std::memcpy(h->dist, d->distortion, sizeof(h->dist));
+  h->W = d.width;
+  h->H = d.height;
+  h->num_points = n_in;  // becomes the number of records (after culling on the cloud path)
+  h->max_fov = d.max_fov;
+  std::memcpy(h->intr, d.intrinsics, sizeof(h->intr));
+  std::memcpy(h->dist, d.distortion, sizeof(h->dist));
   const int B = h->bins;
-  int64_t N = h->num_points;  // becomes the number of records (after culling on the cloud path)
-
-#define CREATE_TRY(expr)                                                                     \
-  do {                                                                                       \
-    hipError_t _e = (expr);                                                                  \
-    if (_e != hipSuccess) {                                                                  \
-      free_handle(h);                                                                        \
-      return fail(NIDREG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));        \
-    }                                                                                        \
-  } while (0)
 
   // ---- tiling: a workgroup owns GW histogram columns (= GW * B cells) in LDS, each cell replicated
   // 2^cshift times (lane-private copies, see k_spline_hist).  Default: ~256 cells x 16 copies = 32 KB.
-  int GW = d->columns_per_group > 0 ? d->columns_per_group : std::max(1, 256 / B);
+  int GW = d.columns_per_group > 0 ? d.columns_per_group : std::max(1, 256 / B);
   GW = std::min(GW, B);
-  int copies = d->lds_copies > 0 ? d->lds_copies : 16;
+  int copies = d.lds_copies > 0 ? d.lds_copies : 16;
   int cshift = 0;
   while ((2 << cshift) <= copies && cshift < 4) cshift++;
   while (size_t(GW) * B * 8 > 128 * 1024 && GW > 1) GW /= 2;
@@ -318,263 +322,243 @@ int create_impl(const nidreg_desc* d, const nidreg_cloud* cloud, const double* T
   // the headline shape (256 bins, one column per workgroup, default tuning) takes the WIDE histogram
   // kernel: 512 threads, 32 copies, one-instruction tap address (k_spline_hist); an explicit
   // lds_copies keeps the generic kernel (tests compare the two bit for bit)
-  h->wide = (d->mode == NIDREG_MODE_SPLINE && B == 256 && GW == 1 && d->lds_copies == 0) ? 1 : 0;
+  h->wide = (d.mode == NIDREG_MODE_SPLINE && B == 256 && GW == 1 && d.lds_copies == 0) ? 1 : 0;
   if (h->wide) cshift = kWideShift;
   h->GW = GW;
   h->cshift = cshift;
   h->NG = (B + GW - 1) / GW;
   h->NEB = (B + kEntropyCols - 1) / kEntropyCols;
-  h->lds_hist = d->mode == NIDREG_MODE_NEAREST ? nearest_hist_lds_bytes(B, GW, cshift) : (size_t(GW) * B * 8 << cshift) + size_t(GW) * 8 + 16;
+  h->lds_hist = d.mode == NIDREG_MODE_NEAREST ? nearest_hist_lds_bytes(B, GW, cshift) : (size_t(GW) * B * 8 << cshift) + size_t(GW) * 8 + 16;
   // gradient pass: a single-column workgroup (GW = 1) keeps ONE copy of its G column (k_spline_grad<.., GW1>)
   h->lds_grad = spline_grad_lds_bytes(B, GW, cshift, false);  // G tile, reduction scratch, phi(q_r), flag (+ staged columns once the table is known to need them)
   h->lds_entropy = size_t(B) * 8 + size_t(GW) * 8 + size_t(kWaves) * 8;
 
   // ---- fixed point: sum over a bin <= N * 2^frac must stay below 2^63
-  const int64_t scaleN = std::max<int64_t>(N, d->scale_points);
+  const int64_t scaleN = std::max<int64_t>(n_in, d.scale_points);
   int nbits = 1;
   while ((int64_t(1) << nbits) <= scaleN) nbits++;
-  h->frac_bits = d->mode == NIDREG_MODE_NEAREST ? 0 : std::min(40, 62 - nbits);
+  h->frac_bits = d.mode == NIDREG_MODE_NEAREST ? 0 : std::min(40, 62 - nbits);
 
-  // ---- everything below is built ON THE DEVICE from one upload of the caller's arrays (the reference constructs
-  // a cost object per pair per outer iteration, visual_camera_calibration.cpp:199-208, so construction time counts):
-  // the bin image, then [ViewCulling::cull ->] histogram column + Morton key -> rocPRIM radix sort -> record gather
-  // (nid_build.hip).  Temporaries live in the per-device scratch arena.
-  const int W = h->W, H = h->H;
-  h->pitch = ((W + 8) + 3) & ~3;  // padded width in pixels
-  const int PH = H + 3;
-  const int nstrips = (PH + 3) / 4 + 1;  // rows are stored in strips of four (nid_device.hpp load_patch)
-  const size_t img_bytes = size_t(h->pitch) * 4 * nstrips + 64;
-  const bool img_f64 = d->image_dtype == NIDREG_IMAGE_F64;
-  if (d->image_dtype != NIDREG_IMAGE_F64 && d->image_dtype != NIDREG_IMAGE_U8) {
-    free_handle(h);
-    return fail(NIDREG_ERR_INVALID, "nidreg_create: bad image_dtype");
-  }
+  // ---- the padded bin image: 1 pixel left / top, >= 2 right / bottom
+  h->pitch = ((h->W + 8) + 3) & ~3;  // padded width in pixels
+  h->img_bytes = size_t(h->pitch) * 4 * image_strips(h->H) + 64;
+}
+
+// A shard: the master handle (same tiling, same bins) has built the padded bin image and the bucketed, Morton-ordered
+// records on the owner device; this shard takes the records of its column groups and a copy of the image
+int take_from_master(nidreg_handle* h, const CreateOpts& opts) {
+  const nidreg_handle* master = opts.master;
+  const int B = h->bins;
+  if (master->GW != h->GW || master->NG != h->NG || master->bins != B || master->pitch != h->pitch || master->img_bytes != h->img_bytes)
+    return fail(NIDREG_ERR_INVALID, "nidreg_create: shard / master layout mismatch");
+  const size_t rec_bytes = master->rec64 ? sizeof(Rec64) : sizeof(Rec32);
+  const int64_t lo = master->gcount[size_t(opts.group_lo)], hi = master->gcount[size_t(opts.group_hi)];
+  HIP_TRY(h->d_img.alloc(h->img_bytes));
+  HIP_TRY(hipMemcpyPeer(h->d_img.as<void>(), h->device, master->d_img.as<void>(), master->device, h->img_bytes));
+  HIP_TRY(h->d_pts.alloc(std::max<size_t>(size_t(hi - lo), 1) * rec_bytes));
+  if (hi > lo) HIP_TRY(hipMemcpyPeer(h->d_pts.as<void>(), h->device, master->d_pts.as<char>() + size_t(lo) * rec_bytes, master->device, size_t(hi - lo) * rec_bytes));
+  h->rec64 = master->rec64;
+  h->gcount.assign(master->gcount.size(), 0);
+  for (size_t g = 0; g < master->gcount.size(); g++) h->gcount[g] = std::min(std::max(master->gcount[g], lo), hi) - lo;
+  h->num_points = hi - lo;
+  h->is_shard = true;
+  h->col_lo = std::min(B, opts.group_lo * h->GW);
+  h->col_hi = std::min(B, opts.group_hi * h->GW);
+  return NIDREG_OK;
+}
+
+// The bin image, then [ViewCulling::cull ->] histogram column + Morton key -> rocPRIM radix sort -> record gather
+// (nid_build.hip).  Temporaries live in the per-device scratch arena, which stays locked for the whole stage.
+int build_on_device(nidreg_handle* h, const nidreg_desc& d, const nidreg_cloud* cloud, const WideBins* wide, const double* T_cull, double min_z, int enable_depth, int64_t n_in) {
+  const int W = h->W, H = h->H, B = h->bins;
+  const bool img_f64 = d.image_dtype == NIDREG_IMAGE_F64;
   const size_t src_row = size_t(W) * (img_f64 ? 8 : 1);
-  if (d->image_row_stride < int64_t(src_row)) {
-    free_handle(h);
-    return fail(NIDREG_ERR_INVALID, "nidreg_create: image_row_stride smaller than a row");
+  const int64_t pstride = d.point_stride > 0 ? d.point_stride : 32;
+  ScratchArena& arena = ScratchArena::of(h->device);
+  std::lock_guard<ScratchArena> guard(arena);
+  const size_t up_img = ((src_row * size_t(H)) + 255) & ~size_t(255);
+  const size_t up_pts = cloud ? 0 : ((size_t(std::max<int64_t>(n_in, 1)) * 32 + 255) & ~size_t(255));
+  const size_t up_int = cloud ? 0 : ((size_t(std::max<int64_t>(n_in, 1)) * 8 + 255) & ~size_t(255));
+  const size_t up_lut = wide ? ((size_t(wide->user_bins) * 2 + 255) & ~size_t(255)) : 0;
+  HIP_TRY(arena.reserve(up_img + up_pts + up_int + 2 * up_lut + build_scratch_bytes(n_in, T_cull != nullptr, W, H) + 4096));
+  const int Bsrc = wide ? wide->user_bins : B;  // the bin count the caller's values are binned with
+  uint16_t *d_lut_img = nullptr, *d_lut_pts = nullptr;
+  if (wide) {
+    d_lut_img = static_cast<uint16_t*>(arena.carve(up_lut));
+    d_lut_pts = static_cast<uint16_t*>(arena.carve(up_lut));
+    HIP_TRY(hipMemcpy(d_lut_img, wide->lut_img.data(), size_t(wide->user_bins) * 2, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_lut_pts, wide->lut_pts.data(), size_t(wide->user_bins) * 2, hipMemcpyHostToDevice));
   }
-  const int64_t pstride = d->point_stride > 0 ? d->point_stride : 32;
-  if (!cloud && n_in > 0 && (pstride < 32 || pstride % 8 != 0)) {
-    free_handle(h);
-    return fail(NIDREG_ERR_INVALID, "nidreg_create: point_stride must be a multiple of 8 and >= 32 ((x y z 1) doubles)");
+
+  // bin image: bin_image = min(int(pix * bins), bins - 1) (nid_cost.hpp:78-79) for CV_64FC1 input;
+  // max(0, min(bins-1, int(u8 / 255.0 * bins))) (cost_calculator_nid.cpp:43-46) for CV_8UC1 input;
+  // padded by 1 (left/top) and >= 2 (right/bottom), edge replicated (= the clamp of knots_x / knots_y, :70-73)
+  void* d_src = arena.carve(up_img);
+  HIP_TRY(h->d_img.alloc(h->img_bytes));
+  HIP_TRY(hipMemcpy2D(d_src, src_row, d.image, size_t(d.image_row_stride), src_row, size_t(H), hipMemcpyHostToDevice));
+  HIP_TRY(build_bin_image_device(d_src, img_f64 ? 1 : 0, (long long)src_row, W, H, Bsrc, d_lut_img, h->pitch, image_strips(H), h->d_img.as<uint8_t>(), nullptr));
+
+  // points: bin_points = max(0, min(bins-1, int(intensity * bins))) (nid_cost.hpp:49, cost_calculator_nid.cpp:47)
+  // is pose independent -> records are bucketed by column group, so a workgroup owns GW histogram columns;
+  // inside a group they follow a Morton curve of the LiDAR-frame bearing (any order gives the same bits -- the
+  // sums are integers --, a spatially coherent one makes a wave's gathers share cache lines for ANY pose).
+  // Records are float32 when that is lossless (PLY data is float32 at source); otherwise double.
+  CullArgs ca;
+  if (T_cull) {
+    ca.model = d.model_id;
+    std::memcpy(ca.intr, d.intrinsics, sizeof(ca.intr));
+    std::memcpy(ca.dist, d.distortion, sizeof(ca.dist));
+    std::memcpy(ca.T, T_cull, sizeof(ca.T));
+    ca.W = d.width;
+    ca.H = d.height;
+    ca.min_z = min_z;
+    ca.depth = enable_depth ? 1 : 0;
   }
-  std::vector<int64_t> gcount;
-  h->img_bytes = img_bytes;
-  if (master) {
-    // a shard: the master handle (same tiling, same bins) has built the padded bin image and the bucketed, Morton-ordered
-    // records on the owner device; this shard takes the records of its column groups and a copy of the image
-    if (master->GW != h->GW || master->NG != h->NG || master->bins != B || master->pitch != h->pitch || master->img_bytes != img_bytes) {
-      free_handle(h);
-      return fail(NIDREG_ERR_INVALID, "nidreg_create: shard / master layout mismatch");
-    }
-    const size_t rec_bytes = master->rec64 ? sizeof(Rec64) : sizeof(Rec32);
-    const int64_t lo = master->gcount[size_t(opts.group_lo)], hi = master->gcount[size_t(opts.group_hi)];
-    CREATE_TRY(hipMalloc(&h->d_img, img_bytes));
-    CREATE_TRY(hipMemcpyPeer(h->d_img, h->device, master->d_img, master->device, img_bytes));
-    CREATE_TRY(hipMalloc(&h->d_pts, std::max<size_t>(size_t(hi - lo), 1) * rec_bytes));
-    if (hi > lo) CREATE_TRY(hipMemcpyPeer(h->d_pts, h->device, static_cast<const char*>(master->d_pts) + size_t(lo) * rec_bytes, master->device, size_t(hi - lo) * rec_bytes));
-    h->rec64 = master->rec64;
-    gcount.assign(master->gcount.size(), 0);
-    for (size_t g = 0; g < master->gcount.size(); g++) gcount[g] = std::min(std::max(master->gcount[g], lo), hi) - lo;
-    N = hi - lo;
-    h->num_points = N;
-    h->is_shard = true;
-    h->col_lo = std::min(B, opts.group_lo * h->GW);
-    h->col_hi = std::min(B, opts.group_hi * h->GW);
-  } else
-  {
-    ScratchArena& arena = ScratchArena::of(h->device);
-    std::lock_guard<ScratchArena> guard(arena);
-    const size_t up_img = ((src_row * size_t(H)) + 255) & ~size_t(255);
-    const size_t up_pts = cloud ? 0 : ((size_t(std::max<int64_t>(n_in, 1)) * 32 + 255) & ~size_t(255));
-    const size_t up_int = cloud ? 0 : ((size_t(std::max<int64_t>(n_in, 1)) * 8 + 255) & ~size_t(255));
-    const size_t up_lut = wide ? ((size_t(wide->user_bins) * 2 + 255) & ~size_t(255)) : 0;
-    CREATE_TRY(arena.reserve(up_img + up_pts + up_int + 2 * up_lut + build_scratch_bytes(n_in, T_cull != nullptr, W, H) + 4096));
-    const int Bsrc = wide ? wide->user_bins : B;  // the bin count the caller's values are binned with
-    uint16_t *d_lut_img = nullptr, *d_lut_pts = nullptr;
-    if (wide) {
-      d_lut_img = static_cast<uint16_t*>(arena.carve(up_lut));
-      d_lut_pts = static_cast<uint16_t*>(arena.carve(up_lut));
-      CREATE_TRY(hipMemcpy(d_lut_img, wide->lut_img.data(), size_t(wide->user_bins) * 2, hipMemcpyHostToDevice));
-      CREATE_TRY(hipMemcpy(d_lut_pts, wide->lut_pts.data(), size_t(wide->user_bins) * 2, hipMemcpyHostToDevice));
-    }
-
-    // bin image: bin_image = min(int(pix * bins), bins - 1) (nid_cost.hpp:78-79) for CV_64FC1 input;
-    // max(0, min(bins-1, int(u8 / 255.0 * bins))) (cost_calculator_nid.cpp:43-46) for CV_8UC1 input;
-    // padded by 1 (left/top) and >= 2 (right/bottom), edge replicated (= the clamp of knots_x / knots_y, :70-73)
-    void* d_src = arena.carve(up_img);
-    CREATE_TRY(hipMalloc(&h->d_img, img_bytes));
-    CREATE_TRY(hipMemcpy2D(d_src, src_row, d->image, size_t(d->image_row_stride), src_row, size_t(H), hipMemcpyHostToDevice));
-    CREATE_TRY(build_bin_image_device(d_src, img_f64 ? 1 : 0, (long long)src_row, W, H, Bsrc, d_lut_img, h->pitch, nstrips, h->d_img, nullptr));
-
-    // points: bin_points = max(0, min(bins-1, int(intensity * bins))) (nid_cost.hpp:49, cost_calculator_nid.cpp:47)
-    // is pose independent -> records are bucketed by column group, so a workgroup owns GW histogram columns;
-    // inside a group they follow a Morton curve of the LiDAR-frame bearing (any order gives the same bits -- the
-    // sums are integers --, a spatially coherent one makes a wave's gathers share cache lines for ANY pose).
-    // Records are float32 when that is lossless (PLY data is float32 at source); otherwise double.
-    CullArgs ca;
-    if (T_cull) {
-      ca.model = d->model_id;
-      std::memcpy(ca.intr, d->intrinsics, sizeof(ca.intr));
-      std::memcpy(ca.dist, d->distortion, sizeof(ca.dist));
-      std::memcpy(ca.T, T_cull, sizeof(ca.T));
-      ca.W = d->width;
-      ca.H = d->height;
-      ca.min_z = min_z;
-      ca.depth = enable_depth ? 1 : 0;
-    }
-    const double* d_cloud_pts = cloud ? cloud->d_pts : nullptr;
-    const double* d_cloud_int = cloud ? cloud->d_int : nullptr;
-    if (!cloud) {
-      double* up_p = static_cast<double*>(arena.carve(up_pts));
-      double* up_i = static_cast<double*>(arena.carve(up_int));
-      if (n_in > 0) {
-        if (pstride == 32) {
-          CREATE_TRY(hipMemcpy(up_p, d->points, size_t(n_in) * 32, hipMemcpyHostToDevice));
-        } else {
-          CREATE_TRY(hipMemcpy2D(up_p, 32, d->points, size_t(pstride), 32, size_t(n_in), hipMemcpyHostToDevice));
-        }
-        CREATE_TRY(hipMemcpy(up_i, d->intensities, size_t(n_in) * 8, hipMemcpyHostToDevice));
+  const double* d_cloud_pts = cloud ? cloud->d_pts.as<double>() : nullptr;
+  const double* d_cloud_int = cloud ? cloud->d_int.as<double>() : nullptr;
+  if (!cloud) {
+    double* up_p = static_cast<double*>(arena.carve(up_pts));
+    double* up_i = static_cast<double*>(arena.carve(up_int));
+    if (n_in > 0) {
+      if (pstride == 32) {
+        HIP_TRY(hipMemcpy(up_p, d.points, size_t(n_in) * 32, hipMemcpyHostToDevice));
+      } else {
+        HIP_TRY(hipMemcpy2D(up_p, 32, d.points, size_t(pstride), 32, size_t(n_in), hipMemcpyHostToDevice));
       }
-      d_cloud_pts = up_p;
-      d_cloud_int = up_i;
+      HIP_TRY(hipMemcpy(up_i, d.intensities, size_t(n_in) * 8, hipMemcpyHostToDevice));
     }
-    void* recs = nullptr;
-    int rec64 = 0;
-    CREATE_TRY(build_records_device(d_cloud_pts, d_cloud_int, n_in, T_cull ? &ca : nullptr, Bsrc, d_lut_pts, GW, h->NG, false, (d->flags & NIDREG_FLAG_INPUT_ORDER) != 0,
-                                    arena, &recs, &rec64, gcount, nullptr));
-    h->d_pts = recs;
-    h->rec64 = rec64;
-    N = gcount[size_t(h->NG)];
-    h->num_points = N;
-    CREATE_TRY(hipStreamSynchronize(nullptr));  // the bin-image kernel, before the arena is handed to the next construction
+    d_cloud_pts = up_p;
+    d_cloud_int = up_i;
   }
+  void* recs = nullptr;
+  int rec64 = 0;
+  HIP_TRY(build_records_device(d_cloud_pts, d_cloud_int, n_in, T_cull ? &ca : nullptr, Bsrc, d_lut_pts, h->GW, h->NG, false, (d.flags & NIDREG_FLAG_INPUT_ORDER) != 0, arena, &recs, &rec64,
+                               h->gcount, nullptr));
+  h->d_pts.adopt(recs);
+  h->rec64 = rec64;
+  h->num_points = h->gcount[size_t(h->NG)];
+  HIP_TRY(hipStreamSynchronize(nullptr));  // the bin-image kernel, before the arena is handed to the next construction
+  return NIDREG_OK;
+}
 
-  // ---- chunk tables (split_groups): by default 4 workgroups per CU for the 256-thread kernels, 2 per CU for the WIDE
-  // histogram kernel (64 KB LDS each), which therefore has its own table
-  {
-    std::vector<uint32_t> gend(static_cast<size_t>(h->NG));
-    for (int g = 0; g < h->NG; g++) gend[size_t(g)] = uint32_t(gcount[size_t(g) + 1]);
-    CREATE_TRY(hipMalloc(&h->d_gend, gend.size() * sizeof(uint32_t)));
-    CREATE_TRY(hipMemcpy(h->d_gend, gend.data(), gend.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    int num_cus = 256;
-    if (hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || num_cus <= 0) num_cus = 256;
-    // (Tried and dropped: emitting a group's parts part-major -- part j of every group in dispatch slot j of the CUs -- and
-    // sizing them by slot weights.  The first-dispatched workgroup of a CU does run ~8 % faster than the second, systematically
-    // (profiles/archive/r03d_workgroup_spread.txt), but the workgroups of one CU share its issue capacity: what ends a pass is the
-    // slowest CU, not the slowest workgroup, and no weighting moved the kernel times (profiles/archive/r03e_slot_weights_no_gain.txt;
-    // the part-major order itself cost 3 us in the gradient pass).)
-    const int max_segs = max_segments(d->mode, GW);
-    auto build_chunks = [&](int target, bool wide_hist, std::vector<Chunk>& chunks) { return split_groups(gcount.data(), h->NG, target, segment_overhead(wide_hist), max_segs, -1, chunks); };
-    // workgroups per CU that are really co-resident for THIS kernel instantiation: 4 for the pinhole family, 3 for the
-    // fisheye / equirectangular gradient kernels (154-161 VGPRs) -- 1024 chunks there meant 1.33 rounds
-    int per_cu_grad = 4, per_cu_hist = h->wide ? 2 : 4;
-    if (d->mode == NIDREG_MODE_SPLINE) {
-      PassArgs oa;
-      fill_pass_args(h, oa);
-      const int og = occupancy_spline_grad<double>(oa);
-      const int oh = occupancy_spline_hist<double>(oa);
-      if (og > 0) per_cu_grad = std::min(og, 8);
-      if (oh > 0) per_cu_hist = std::min(oh, 8);
-    } else {  // NEAREST: the fast-tier kernels of the wide-angle models hold three (equirectangular) or four waves per SIMD
-      PassArgs oa;
-      fill_pass_args(h, oa);
-      const int on = occupancy_nearest_hist<double>(oa);
-      if (on > 0) per_cu_grad = per_cu_hist = std::min(on, 4);
-    }
-    h->gcount = gcount;
-    h->num_cus = num_cus;
-    h->per_cu_grad = h->wide ? per_cu_grad : std::min(per_cu_grad, per_cu_hist);
-    h->per_cu_hist = per_cu_hist;
-    std::vector<Chunk> chunks;
-    auto own_target = [&](int per_cu) {
-      if (d->target_blocks > 0) return int(d->target_blocks);
-      const int64_t full = int64_t(per_cu) * num_cus;
-      return int(snap_to_groups(round_chunks(per_cu, num_cus, N), gcount.data(), h->NG, full));
-    };
-    h->nslots = int(build_chunks(own_target(h->per_cu_grad), false, chunks));
-    h->nchunks = int(chunks.size());
-    for (const Chunk& c : chunks) h->longest_chunk = std::max<int64_t>(h->longest_chunk, c.count);
-    h->seg = h->nslots > h->nchunks ? 1 : 0;
-    if (h->seg && GW == 1) h->lds_grad = spline_grad_lds_bytes(B, GW, cshift, true);
-    h->chunks_cap = std::max<size_t>(chunks.size(), 1);
-    CREATE_TRY(hipMalloc(&h->d_chunks, h->chunks_cap * sizeof(Chunk)));
-    if (!chunks.empty()) CREATE_TRY(hipMemcpy(h->d_chunks, chunks.data(), chunks.size() * sizeof(Chunk), hipMemcpyHostToDevice));
-    if (h->wide) {
-      std::vector<Chunk> wide_chunks;
-      const int64_t wide_slots = build_chunks(own_target(per_cu_hist), true, wide_chunks);
-      h->nchunks_hist = int(wide_chunks.size());
-      h->seg_hist = wide_slots > int64_t(wide_chunks.size()) ? 1 : 0;
-      h->chunks_hist_cap = std::max<size_t>(wide_chunks.size(), 1);
-      CREATE_TRY(hipMalloc(&h->d_chunks_hist, h->chunks_hist_cap * sizeof(Chunk)));
-      if (!wide_chunks.empty()) CREATE_TRY(hipMemcpy(h->d_chunks_hist, wide_chunks.data(), wide_chunks.size() * sizeof(Chunk), hipMemcpyHostToDevice));
-    }
+// ---- chunk tables (split_groups): by default 4 workgroups per CU for the 256-thread kernels, 2 per CU for the WIDE
+// histogram kernel (64 KB LDS each), which therefore has its own table
+int plan_chunk_tables(nidreg_handle* h, const nidreg_desc& d) {
+  const int B = h->bins, GW = h->GW;
+  const std::vector<int64_t>& gcount = h->gcount;
+  std::vector<uint32_t> gend(static_cast<size_t>(h->NG));
+  for (int g = 0; g < h->NG; g++) gend[size_t(g)] = uint32_t(gcount[size_t(g) + 1]);
+  HIP_TRY(h->d_gend.alloc(gend.size() * sizeof(uint32_t)));
+  HIP_TRY(hipMemcpy(h->d_gend.as<void>(), gend.data(), gend.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  int num_cus = 256;
+  if (hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || num_cus <= 0) num_cus = 256;
+  // (Tried and dropped: emitting a group's parts part-major -- part j of every group in dispatch slot j of the CUs -- and
+  // sizing them by slot weights.  The first-dispatched workgroup of a CU does run ~8 % faster than the second, systematically
+  // (profiles/archive/r03d_workgroup_spread.txt), but the workgroups of one CU share its issue capacity: what ends a pass is the
+  // slowest CU, not the slowest workgroup, and no weighting moved the kernel times (profiles/archive/r03e_slot_weights_no_gain.txt;
+  // the part-major order itself cost 3 us in the gradient pass).)
+  const int max_segs = max_segments(d.mode, GW);
+  auto build_chunks = [&](int target, bool wide_hist, std::vector<Chunk>& chunks) { return split_groups(gcount.data(), h->NG, target, segment_overhead(wide_hist), max_segs, -1, chunks); };
+  // workgroups per CU that are really co-resident for THIS kernel instantiation: 4 for the pinhole family, 3 for the
+  // fisheye / equirectangular gradient kernels (154-161 VGPRs) -- 1024 chunks there meant 1.33 rounds
+  int per_cu_grad = 4, per_cu_hist = h->wide ? 2 : 4;
+  if (d.mode == NIDREG_MODE_SPLINE) {
+    PassArgs oa;
+    fill_pass_args(h, oa);
+    const int og = occupancy_spline_grad<double>(oa);
+    const int oh = occupancy_spline_hist<double>(oa);
+    if (og > 0) per_cu_grad = std::min(og, 8);
+    if (oh > 0) per_cu_hist = std::min(oh, 8);
+  } else {  // NEAREST: the fast-tier kernels of the wide-angle models hold three (equirectangular) or four waves per SIMD
+    PassArgs oa;
+    fill_pass_args(h, oa);
+    const int on = occupancy_nearest_hist<double>(oa);
+    if (on > 0) per_cu_grad = per_cu_hist = std::min(on, 4);
   }
+  h->num_cus = num_cus;
+  h->per_cu_grad = h->wide ? per_cu_grad : std::min(per_cu_grad, per_cu_hist);
+  h->per_cu_hist = per_cu_hist;
+  std::vector<Chunk> chunks;
+  auto own_target = [&](int per_cu) {
+    if (d.target_blocks > 0) return int(d.target_blocks);
+    const int64_t full = int64_t(per_cu) * num_cus;
+    return int(snap_to_groups(round_chunks(per_cu, num_cus, h->num_points), gcount.data(), h->NG, full));
+  };
+  h->nslots = int(build_chunks(own_target(h->per_cu_grad), false, chunks));
+  h->nchunks = int(chunks.size());
+  for (const Chunk& c : chunks) h->longest_chunk = std::max<int64_t>(h->longest_chunk, c.count);
+  h->seg = h->nslots > h->nchunks ? 1 : 0;
+  if (h->seg && GW == 1) h->lds_grad = spline_grad_lds_bytes(B, GW, h->cshift, true);
+  h->chunks_cap = std::max<size_t>(chunks.size(), 1);
+  HIP_TRY(h->d_chunks.alloc(h->chunks_cap * sizeof(Chunk)));
+  if (!chunks.empty()) HIP_TRY(hipMemcpy(h->d_chunks.as<void>(), chunks.data(), chunks.size() * sizeof(Chunk), hipMemcpyHostToDevice));
+  if (h->wide) {
+    std::vector<Chunk> wide_chunks;
+    const int64_t wide_slots = build_chunks(own_target(per_cu_hist), true, wide_chunks);
+    h->nchunks_hist = int(wide_chunks.size());
+    h->seg_hist = wide_slots > int64_t(wide_chunks.size()) ? 1 : 0;
+    h->chunks_hist_cap = std::max<size_t>(wide_chunks.size(), 1);
+    HIP_TRY(h->d_chunks_hist.alloc(h->chunks_hist_cap * sizeof(Chunk)));
+    if (!wide_chunks.empty()) HIP_TRY(hipMemcpy(h->d_chunks_hist.as<void>(), wide_chunks.data(), wide_chunks.size() * sizeof(Chunk), hipMemcpyHostToDevice));
+  }
+  return NIDREG_OK;
+}
 
-  // ---- NEAREST on an equirectangular camera: the pixel-boundary tables of the fast decision tier (nid_kernels.hpp NearestFast).
-  // Boundary u = k sits at longitude theta_k = 2 pi (k / W - 1/2), boundary v = j at latitude pi (j / H - 1/2), W and H the
-  // INTRINSICS (equirectangular.hpp:14-28 projects with them; the image size only enters the in-image test).
-  if (d->mode == NIDREG_MODE_NEAREST && h->model == NIDREG_MODEL_EQUIRECTANGULAR && h->intr[0] >= 8.0 && h->intr[1] >= 8.0 && h->intr[0] <= 65536.0 && h->intr[1] <= 65536.0) {
-    const double pi = 3.14159265358979323846;
-    h->eq_kmax = int(std::ceil(h->intr[0]));
-    h->eq_jmax = int(std::ceil(h->intr[1]));
-    std::vector<double> tab(2 * size_t(h->eq_kmax + 1) + size_t(h->eq_jmax + 1));
-    for (int k = 0; k <= h->eq_kmax; k++) {
-      const double th = 2.0 * pi * (double(k) / h->intr[0] - 0.5);
-      tab[2 * size_t(k)] = std::cos(th);
-      tab[2 * size_t(k) + 1] = std::sin(th);
-    }
-    for (int j = 0; j <= h->eq_jmax; j++) {
-      const double sj = std::sin(pi * (double(j) / h->intr[1] - 0.5));
-      tab[2 * size_t(h->eq_kmax + 1) + size_t(j)] = sj * std::fabs(sj);
-    }
-    CREATE_TRY(hipMalloc(&h->d_eq_tab, tab.size() * sizeof(double)));
-    CREATE_TRY(hipMemcpy(h->d_eq_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+// ---- NEAREST on an equirectangular camera: the pixel-boundary tables of the fast decision tier (nid_kernels.hpp NearestFast).
+// Boundary u = k sits at longitude theta_k = 2 pi (k / W - 1/2), boundary v = j at latitude pi (j / H - 1/2), W and H the
+// INTRINSICS (equirectangular.hpp:14-28 projects with them; the image size only enters the in-image test).
+int build_equirect_tables(nidreg_handle* h) {
+  if (h->mode != NIDREG_MODE_NEAREST || h->model != NIDREG_MODEL_EQUIRECTANGULAR || h->intr[0] < 8.0 || h->intr[1] < 8.0 || h->intr[0] > 65536.0 || h->intr[1] > 65536.0) return NIDREG_OK;
+  const double pi = 3.14159265358979323846;
+  h->eq_kmax = int(std::ceil(h->intr[0]));
+  h->eq_jmax = int(std::ceil(h->intr[1]));
+  std::vector<double> tab(2 * size_t(h->eq_kmax + 1) + size_t(h->eq_jmax + 1));
+  for (int k = 0; k <= h->eq_kmax; k++) {
+    const double th = 2.0 * pi * (double(k) / h->intr[0] - 0.5);
+    tab[2 * size_t(k)] = std::cos(th);
+    tab[2 * size_t(k) + 1] = std::sin(th);
   }
+  for (int j = 0; j <= h->eq_jmax; j++) {
+    const double sj = std::sin(pi * (double(j) / h->intr[1] - 0.5));
+    tab[2 * size_t(h->eq_kmax + 1) + size_t(j)] = sj * std::fabs(sj);
+  }
+  HIP_TRY(h->d_eq_tab.alloc(tab.size() * sizeof(double)));
+  HIP_TRY(hipMemcpy(h->d_eq_tab.as<void>(), tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+  return NIDREG_OK;
+}
 
-#ifdef NID_EXP_HANDOFF
-  {  // EXPERIMENT: the (u, v) hand-off buffer of the process' one handle (leaked at destruction: an experiment build)
-    void* uvb = nullptr;
-    CREATE_TRY(hipMalloc(&uvb, size_t(std::max<int64_t>(N, 1)) * 16 + 64));
-    CREATE_TRY(hipMemset(uvb, 0, size_t(std::max<int64_t>(N, 1)) * 16 + 64));
-    CREATE_TRY(set_handoff_buffer(uvb));
-  }
-#endif
-  // ---- per-evaluation scratch
+// ---- per-evaluation state: the stream, the histogram double buffer, the result block, the scratch, the host block, the events
+int alloc_eval_state(nidreg_handle* h, const nidreg_desc& d, bool shard) {
+  const int B = h->bins;
   h->hist_words = nidreg_hist_words(B);
-  if (d->ext_stream || (d->flags & NIDREG_FLAG_EXT_STREAM)) {
-    h->stream = static_cast<hipStream_t>(d->ext_stream);
+  const size_t hist_bytes = size_t(h->hist_words) * sizeof(u64);
+  if (d.ext_stream || (d.flags & NIDREG_FLAG_EXT_STREAM)) {
+    h->stream = static_cast<hipStream_t>(d.ext_stream);
   } else {
-    CREATE_TRY(pool_stream(h->device, &h->stream));
+    HIP_TRY(pool_stream(h->device, &h->stream));
     h->own_stream = true;
   }
-  if (d->ext_hist) {
-    h->d_hist = static_cast<u64*>(d->ext_hist);
+  if (d.ext_hist) {
+    h->d_hist = static_cast<u64*>(d.ext_hist);
   } else {
-    if (opts.shard) {
-      // a shard's two buffers are replicas of the WHOLE pair's histogram: the owners of the other columns store into them from
-      // their own devices (nid_kernels.hpp k_entropy_repl) -- fine-grained (coherent) device memory, mapped into every peer
-      CREATE_TRY(hipExtMallocWithFlags(reinterpret_cast<void**>(&h->d_hist_buf[0]), size_t(h->hist_words) * sizeof(u64), hipDeviceMallocFinegrained));
-      CREATE_TRY(hipExtMallocWithFlags(reinterpret_cast<void**>(&h->d_hist_buf[1]), size_t(h->hist_words) * sizeof(u64), hipDeviceMallocFinegrained));
-    } else {
-      CREATE_TRY(hipMalloc(&h->d_hist_buf[0], size_t(h->hist_words) * sizeof(u64)));
-      CREATE_TRY(hipMalloc(&h->d_hist_buf[1], size_t(h->hist_words) * sizeof(u64)));
-    }
-    CREATE_TRY(hipMemset(h->d_hist_buf[1], 0, size_t(h->hist_words) * sizeof(u64)));
-    h->d_hist = h->d_hist_buf[0];
+    // a shard's two buffers are replicas of the WHOLE pair's histogram: the owners of the other columns store into them from
+    // their own devices (nid_kernels.hpp k_entropy_repl) -- fine-grained (coherent) device memory, mapped into every peer
+    for (DeviceBuf& buf : h->d_hist_buf) HIP_TRY(shard ? buf.alloc_finegrained(hist_bytes) : buf.alloc(hist_bytes));
+    HIP_TRY(hipMemset(h->d_hist_buf[1].as<void>(), 0, hist_bytes));
+    h->d_hist = h->d_hist_buf[0].as<u64>();
     h->hist_cur = 0;
     h->hist_zeroed[1] = true;  // [0] is zeroed below and read by nidreg_get_hist before the first evaluation
     h->own_hist = true;
   }
-  if (d->ext_out) {
-    h->d_out = static_cast<double*>(d->ext_out);
+  if (d.ext_out) {
+    h->d_out = static_cast<double*>(d.ext_out);
   } else {
-    CREATE_TRY(hipMalloc(&h->d_out, NIDREG_OUT_DOUBLES * sizeof(double)));
+    HIP_TRY(h->d_out_buf.alloc(NIDREG_OUT_DOUBLES * sizeof(double)));
+    h->d_out = h->d_out_buf.as<double>();
     h->own_out = true;
   }
-  CREATE_TRY(hipMemset(h->d_out, 0, NIDREG_OUT_DOUBLES * sizeof(double)));
-  CREATE_TRY(hipMemset(h->d_hist, 0, size_t(h->hist_words) * sizeof(u64)));
+  HIP_TRY(hipMemset(h->d_out, 0, NIDREG_OUT_DOUBLES * sizeof(double)));
+  HIP_TRY(hipMemset(h->d_hist, 0, hist_bytes));
   {
     // one allocation, carved (256-byte aligned) and zeroed: nidreg_get_hist before the first evaluation then
     // reads zeros, not uninitialised memory
@@ -593,9 +577,9 @@ int create_impl(const nidreg_desc* d, const nidreg_cloud* cloud, const double* T
     h->partials_cap = partial_slots(h);
     const size_t o_partials = carve(size_t(h->partials_cap) * 12 * sizeof(double));
     const size_t o_counters = carve(8 * sizeof(unsigned int));
-    CREATE_TRY(hipMalloc(&h->d_scratch, off));
-    CREATE_TRY(hipMemset(h->d_scratch, 0, off));
-    char* base = static_cast<char*>(h->d_scratch);
+    HIP_TRY(h->d_scratch.alloc(off));
+    HIP_TRY(hipMemset(h->d_scratch.as<void>(), 0, off));
+    char* base = h->d_scratch.as<char>();
     h->d_part_hj = reinterpret_cast<long long*>(base + o_part_hj);
     h->d_row_part = reinterpret_cast<u64*>(base + o_row_part);
     h->d_phi_q = reinterpret_cast<double*>(base + o_phi_q);
@@ -607,23 +591,56 @@ int create_impl(const nidreg_desc* d, const nidreg_cloud* cloud, const double* T
   }
   {
     void* blk = nullptr;
-    CREATE_TRY(pool_host_block(h->device, false, NIDREG_OUT_DOUBLES * sizeof(double), &blk));
+    HIP_TRY(pool_host_block(h->device, false, NIDREG_OUT_DOUBLES * sizeof(double), &blk));
     h->h_out = static_cast<double*>(blk);
   }
   std::memset(h->h_out, 0, NIDREG_OUT_DOUBLES * sizeof(double));
-  if (!d->ext_out) {
+  if (!d.ext_out) {
     // results are written straight into host-mapped memory by the finalising workgroups: no D2H copy
     void* dp = nullptr;
-    CREATE_TRY(hipHostGetDevicePointer(&dp, h->h_out, 0));
+    HIP_TRY(hipHostGetDevicePointer(&dp, h->h_out, 0));
     h->d_out_host = static_cast<double*>(dp);
   }
-  for (int i = 0; i < 6; i++) CREATE_TRY(hipEventCreate(&h->ev[i]));
+  for (int i = 0; i < 6; i++) HIP_TRY(hipEventCreate(&h->ev[i]));
   // The clears above (result block, histogram buffers, scratch incl. the ticket counters) are hipMemset calls on the null
   // stream, which return before they have run (2.9 us per call in the API trace, profiles/archive/r04m_hip_api_stats.csv), and the
   // handle's own stream is non-blocking: the first evaluation must not be able to overtake them.
-  CREATE_TRY(hipStreamSynchronize(nullptr));
-#undef CREATE_TRY
-  *out = h;
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  return NIDREG_OK;
+}
+
+}  // namespace
+
+int create_impl(const nidreg_desc* d, const nidreg_cloud* cloud, const double* T_cull, double min_z, int enable_depth, const CreateOpts& opts, nidreg_handle** out) {
+  if (!d || !out) return fail(NIDREG_ERR_INVALID, "nidreg_create: null argument");
+  *out = nullptr;
+  nidreg_desc dd;  // the caller's desc, with the compact bin count when bins > 256
+  WideBins wide_here;
+  const WideBins* wide = nullptr;
+  int64_t n_in = 0;
+  int rc = check_desc(d, cloud, opts, dd, wide_here, wide, n_in);
+  if (rc == NIDREG_OK) rc = use_device("nidreg_create", dd.device_id, " (the NID core has no CPU path)");
+  if (rc == NIDREG_OK) rc = check_after_device(dd, cloud, n_in);
+  if (rc) return rc;
+  const nidreg_handle* master = opts.shard ? opts.master : nullptr;
+  std::unique_ptr<nidreg_handle, void (*)(nidreg_handle*)> h(new nidreg_handle(), free_handle);  // a stage that fails: the handle is freed here
+  plan_tiling(h.get(), dd, wide, master, n_in);
+  rc = master ? take_from_master(h.get(), opts) : build_on_device(h.get(), dd, cloud, wide, T_cull, min_z, enable_depth, n_in);
+  if (rc == NIDREG_OK) rc = plan_chunk_tables(h.get(), dd);
+  if (rc == NIDREG_OK) rc = build_equirect_tables(h.get());
+  if (rc) return rc;
+#ifdef NID_EXP_HANDOFF
+  {  // EXPERIMENT: the (u, v) hand-off buffer of the process' one handle (leaked at destruction: an experiment build)
+    void* uvb = nullptr;
+    const int64_t N = h->num_points;
+    HIP_TRY(hipMalloc(&uvb, size_t(std::max<int64_t>(N, 1)) * 16 + 64));
+    HIP_TRY(hipMemset(uvb, 0, size_t(std::max<int64_t>(N, 1)) * 16 + 64));
+    HIP_TRY(set_handoff_buffer(uvb));
+  }
+#endif
+  rc = alloc_eval_state(h.get(), dd, opts.shard);
+  if (rc) return rc;
+  *out = h.release();
   return NIDREG_OK;
 }
 }  // namespace nidreg_detail

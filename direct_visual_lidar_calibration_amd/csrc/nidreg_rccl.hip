@@ -53,14 +53,15 @@ int rccl_check_agreement(nidreg_handle* h, ncclComm_t comm, const char* who) {
   const int kN = 5;
   long long v[2 * kN] = {h->frac_bits, h->bins, (long long)h->hist_words, h->mode, h->bins_user};
   for (int k = 0; k < kN; k++) v[kN + k] = -v[k];
-  long long* d = nullptr;
-  HIP_TRY(hipMalloc(&d, sizeof(v)));
+  DeviceBuf buf;
+  HIP_TRY(buf.alloc(sizeof(v)));
+  long long* d = buf.as<long long>();
   hipError_t e = hipMemcpyAsync(d, v, sizeof(v), hipMemcpyHostToDevice, h->stream);
   ncclResult_t r = ncclSuccess;
   if (e == hipSuccess) r = api->AllReduce(d, d, size_t(2 * kN), ncclInt64, ncclMax, comm, h->stream);
   if (e == hipSuccess && r == ncclSuccess) e = hipMemcpyAsync(v, d, sizeof(v), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess && r == ncclSuccess) e = hipStreamSynchronize(h->stream);
-  (void)hipFree(d);
+  (void)buf.reset();
   if (r != ncclSuccess) return rccl_fail(who, r);
   if (e != hipSuccess) return fail(NIDREG_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
   static const char* names[kN] = {"frac_bits (desc.scale_points must be the pair's TOTAL point count on every rank)", "bins", "hist_words", "mode", "bins (caller's count)"};

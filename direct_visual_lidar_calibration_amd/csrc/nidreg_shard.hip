@@ -66,8 +66,8 @@ int shard_launch_phase(ShardSet* set, int g, int phase, bool alone) {
     const int role = set->colocated ? (phase == 1 ? SHARD_PUSH : SHARD_REDUCE) : (SHARD_PUSH | SHARD_REDUCE);
     if (phase == 2 && !set->colocated) return NIDREG_OK;
     const bool reduces = (role & SHARD_REDUCE) != 0;
-    hipLaunchKernelGGL(k_entropy_repl, dim3(set->nblocks), dim3(kEntropyThreads), 0, h->stream, h->d_hist, h->bins, 1.0 / fixed_unit(h), h->d_shard_tab, set->seq, h->hist_cur, role, h->d_phi_q,
-                       h->d_hist_image, h->d_hist_points, h->d_scal, h->d_out, h->d_out_host, grad ? 0.0 : h->seq, h->d_counters, reduces ? h->d_hist_buf[h->hist_cur ^ 1] : nullptr, h->hist_words,
+    hipLaunchKernelGGL(k_entropy_repl, dim3(set->nblocks), dim3(kEntropyThreads), 0, h->stream, h->d_hist, h->bins, 1.0 / fixed_unit(h), h->d_shard_tab.as<ShardTable>(), set->seq, h->hist_cur, role, h->d_phi_q,
+                       h->d_hist_image, h->d_hist_points, h->d_scal, h->d_out, h->d_out_host, grad ? 0.0 : h->seq, h->d_counters, reduces ? h->d_hist_buf[h->hist_cur ^ 1].as<u64>() : nullptr, h->hist_words,
                        grad_runs_tail ? 0 : 1, h->d_out + 10, h->d_out_host ? h->d_out_host + 10 : nullptr, set->timeout_ticks);
     HIP_TRY(hipGetLastError());
     if (reduces) {
@@ -231,8 +231,8 @@ void free_shard_set(ShardSet* set) {
   for (size_t g = 0; g < set->shards.size(); g++) {
     if (!set->shards[g]) continue;
     (void)hipSetDevice(set->shards[g]->device);
-    if (g < set->flags.size() && set->flags[g]) (void)hipFree(set->flags[g]);
-    if (g < set->gather.size() && set->gather[g]) (void)hipFree(set->gather[g]);
+    (void)set->flags[g].reset();  // (every shard's stream was drained above)
+    (void)set->gather[g].reset();
   }
   for (size_t g = 1; g < set->shards.size(); g++) free_handle(set->shards[g]);
   delete set;
@@ -268,7 +268,7 @@ int create_sharded(const nidreg_desc* d, const nidreg_cloud* cloud, const double
   if (d->bins < 2 || d->bins > kMaxWideBins) return fail(NIDREG_ERR_INVALID, "nidreg_create: bins must be in [2, " + std::to_string(kMaxWideBins) + "]");
   if (d->image_dtype != NIDREG_IMAGE_F64 && d->image_dtype != NIDREG_IMAGE_U8) return fail(NIDREG_ERR_INVALID, "nidreg_create: bad image_dtype");
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(NIDREG_ERR_NO_DEVICE, "nidreg_create: no HIP device (the NID core has no CPU path)");
+  if (const int rc = count_devices("nidreg_create", &ndev, " (the NID core has no CPU path)")) return rc;
   for (int id : ids)
     if (id < 0 || id >= ndev) return fail(NIDREG_ERR_INVALID, "nidreg_create: device id " + std::to_string(id) + " out of range (NIDREG_DEVICES / desc.device_ids)");
   // peer mappings, both directions, before any buffer is allocated
@@ -331,8 +331,8 @@ int create_sharded(const nidreg_desc* d, const nidreg_cloud* cloud, const double
   set->CB = CB;
   set->nblocks = (B + CB - 1) / CB;
   set->shards.assign(size_t(n), nullptr);
-  set->flags.assign(size_t(n), nullptr);
-  set->gather.assign(size_t(n), nullptr);
+  set->flags.resize(size_t(n));
+  set->gather.resize(size_t(n));
   set->rc.assign(size_t(n), 0);
   set->res.assign(size_t(n), std::array<double, 8>());
   set->lock_devices = ids;
@@ -384,10 +384,10 @@ int create_sharded(const nidreg_desc* d, const nidreg_cloud* cloud, const double
     nidreg_handle* h = set->shards[size_t(g)];
     h->shard_index = g;
     hipError_t e = hipSetDevice(h->device);
-    if (e == hipSuccess) e = hipExtMallocWithFlags(reinterpret_cast<void**>(&set->flags[size_t(g)]), kFlagWords * sizeof(u64), hipDeviceMallocFinegrained);
-    if (e == hipSuccess) e = hipMemset(set->flags[size_t(g)], 0, kFlagWords * sizeof(u64));
-    if (e == hipSuccess) e = hipExtMallocWithFlags(reinterpret_cast<void**>(&set->gather[size_t(g)]), gw * sizeof(u64), hipDeviceMallocFinegrained);
-    if (e == hipSuccess) e = hipMemset(set->gather[size_t(g)], 0, gw * sizeof(u64));
+    if (e == hipSuccess) e = set->flags[size_t(g)].alloc_finegrained(kFlagWords * sizeof(u64));
+    if (e == hipSuccess) e = hipMemset(set->flags[size_t(g)].as<void>(), 0, kFlagWords * sizeof(u64));
+    if (e == hipSuccess) e = set->gather[size_t(g)].alloc_finegrained(gw * sizeof(u64));
+    if (e == hipSuccess) e = hipMemset(set->gather[size_t(g)].as<void>(), 0, gw * sizeof(u64));
     if (e != hipSuccess) return bail(fail(NIDREG_ERR_HIP, std::string("sharded handle: flag / gather block: ") + hipGetErrorString(e)));
   }
   for (int g = 0; g < n; g++) {
@@ -395,10 +395,10 @@ int create_sharded(const nidreg_desc* d, const nidreg_cloud* cloud, const double
     ShardTable tab;
     std::memset(&tab, 0, sizeof(tab));
     for (int p = 0; p < n; p++) {
-      tab.flags[p] = set->flags[size_t(p)];
-      tab.gather[p] = set->gather[size_t(p)];
-      tab.hist[p][0] = set->shards[size_t(p)]->d_hist_buf[0];
-      tab.hist[p][1] = set->shards[size_t(p)]->d_hist_buf[1];
+      tab.flags[p] = set->flags[size_t(p)].as<u64>();
+      tab.gather[p] = set->gather[size_t(p)].as<u64>();
+      tab.hist[p][0] = set->shards[size_t(p)]->d_hist_buf[0].as<u64>();
+      tab.hist[p][1] = set->shards[size_t(p)]->d_hist_buf[1].as<u64>();
       tab.cut[p] = set->shards[size_t(p)]->col_lo;
     }
     tab.cut[n] = B;
@@ -408,8 +408,8 @@ int create_sharded(const nidreg_desc* d, const nidreg_cloud* cloud, const double
     tab.col_lo = h->col_lo;
     tab.col_hi = h->col_hi;
     hipError_t e = hipSetDevice(h->device);
-    if (e == hipSuccess) e = hipMalloc(&h->d_shard_tab, sizeof(ShardTable));
-    if (e == hipSuccess) e = hipMemcpy(h->d_shard_tab, &tab, sizeof(ShardTable), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = h->d_shard_tab.alloc(sizeof(ShardTable));
+    if (e == hipSuccess) e = hipMemcpy(h->d_shard_tab.as<void>(), &tab, sizeof(ShardTable), hipMemcpyHostToDevice);
     if (e != hipSuccess) return bail(fail(NIDREG_ERR_HIP, std::string("sharded handle: shard table: ") + hipGetErrorString(e)));
   }
   free_handle(master);
@@ -426,22 +426,21 @@ int create_sharded(const nidreg_desc* d, const nidreg_cloud* cloud, const double
       for (int b = 0; b < n; b++) {
         nidreg_handle *ha = set->shards[size_t(a)], *hb = set->shards[size_t(b)];
         if (a == b || ha->device == hb->device) continue;
-        u64 *oa = nullptr, *ob = nullptr;  // host-mapped result words
-        hipError_t e = hipHostMalloc(&oa, 2 * sizeof(u64), hipHostMallocMapped);
-        if (e == hipSuccess) e = hipHostMalloc(&ob, 2 * sizeof(u64), hipHostMallocMapped);
+        HostBuf words_a, words_b;  // host-mapped result words
+        hipError_t e = words_a.alloc(2 * sizeof(u64), hipHostMallocMapped);
+        if (e == hipSuccess) e = words_b.alloc(2 * sizeof(u64), hipHostMallocMapped);
         if (e != hipSuccess) return bail(fail(NIDREG_ERR_HIP, std::string("shard self-test: ") + hipGetErrorString(e)));
+        u64 *oa = words_a.as<u64>(), *ob = words_b.as<u64>();
         oa[0] = oa[1] = ob[0] = ob[1] = 0;
         const u64 pattern = 0x5e1f7e5700000000ull | (u64(a) << 8) | u64(b);
         (void)hipSetDevice(hb->device);
-        hipLaunchKernelGGL(k_shard_selftest_pong, dim3(1), dim3(64), 0, hb->stream, hb->d_shard_tab, a, seq, pattern, ob, ticks);
+        hipLaunchKernelGGL(k_shard_selftest_pong, dim3(1), dim3(64), 0, hb->stream, hb->d_shard_tab.as<ShardTable>(), a, seq, pattern, ob, ticks);
         (void)hipSetDevice(ha->device);
-        hipLaunchKernelGGL(k_shard_selftest_ping, dim3(1), dim3(64), 0, ha->stream, ha->d_shard_tab, b, seq, pattern, oa, ticks);
+        hipLaunchKernelGGL(k_shard_selftest_ping, dim3(1), dim3(64), 0, ha->stream, ha->d_shard_tab.as<ShardTable>(), b, seq, pattern, oa, ticks);
         e = hipStreamSynchronize(ha->stream);
         (void)hipSetDevice(hb->device);
         if (e == hipSuccess) e = hipStreamSynchronize(hb->stream);
         const u64 ra = oa[0], rb = ob[0], rtt = oa[1];
-        (void)hipHostFree(oa);
-        (void)hipHostFree(ob);
         char line[200];
         std::snprintf(line, sizeof(line), "nidreg shard self-test: device %d -> device %d: %s%s, round trip %.1f us\n", ha->device, hb->device,
                       rb == 1 ? "flag and payload visible" : (rb == 3 ? "PAYLOAD NOT VISIBLE BEHIND THE FLAG" : "FLAG NEVER ARRIVED"), ra == 1 ? ", answer seen" : ", NO ANSWER", double(rtt) * 0.01);
@@ -456,8 +455,8 @@ int create_sharded(const nidreg_desc* d, const nidreg_cloud* cloud, const double
     // flags and payload words back to zero: the evaluations' sequence numbers start at 1
     for (int g = 0; g < n; g++) {
       (void)hipSetDevice(set->shards[size_t(g)]->device);
-      (void)hipMemset(set->flags[size_t(g)], 0, kFlagWords * sizeof(u64));
-      (void)hipMemset(set->gather[size_t(g)], 0, gw * sizeof(u64));
+      (void)hipMemset(set->flags[size_t(g)].as<void>(), 0, kFlagWords * sizeof(u64));
+      (void)hipMemset(set->gather[size_t(g)].as<void>(), 0, gw * sizeof(u64));
     }
   }
   if (!set->colocated)
