@@ -195,13 +195,10 @@ static int async_submit(nidreg_handle* h, int mode, const double* pose, bool wan
     HIP_TRY(hipHostGetDevicePointer(&dp, h->h_ring, 0));
     h->d_ring = static_cast<double*>(dp);
   }
-  // the launch helpers write to h->d_out_host with tag h->seq: point them at this evaluation's ring block for the launch
-  double* const own = h->d_out_host;
-  h->d_out_host = h->d_ring + size_t(t % kAsyncDepth) * NIDREG_OUT_DOUBLES;
+  double* const slot = h->d_ring + size_t(t % kAsyncDepth) * NIDREG_OUT_DOUBLES;  // this evaluation's results and tag (h->seq) go to its ring block
   // alone on the device = nothing in flight but this handle's own earlier submissions (they run before it, in stream order)
   const bool alone = h->device >= 0 && h->device < NIDREG_MAX_DEVICES && g_inflight[h->device].fetch_add(1, std::memory_order_acq_rel) == h->async_outstanding;
-  const int rc = mode == NIDREG_MODE_SPLINE ? eval_launch(h, pose, want_grad, alone) : iso_launch(h, pose);
-  h->d_out_host = own;
+  const int rc = mode == NIDREG_MODE_SPLINE ? eval_launch(h, pose, want_grad, alone, slot) : iso_launch(h, pose, slot);
   if (rc) {
     if (h->device >= 0 && h->device < NIDREG_MAX_DEVICES) g_inflight[h->device].fetch_sub(1, std::memory_order_acq_rel);
     return rc;
@@ -291,10 +288,28 @@ int nidreg_eval_iso(nidreg_handle* h, const double* T, double* cost) {
   if (h->set) return set_eval(h->set, NIDREG_MODE_NEAREST, T, cost, nullptr) < 0 ? NIDREG_ERR_HIP : NIDREG_OK;
   if (h->rccl_comm) return rccl_eval(h, NIDREG_MODE_NEAREST, T, cost, nullptr) < 0 ? NIDREG_ERR_HIP : NIDREG_OK;
   cohort_check(h);
-  const int rc = iso_launch(h, T);
-  if (rc) return rc;
+  RC_TRY(iso_launch(h, T));
   return eval_finish(h, cost, nullptr) < 0 ? NIDREG_ERR_HIP : NIDREG_OK;  // CostCalculatorNID has no finite check
 }
+
+// the sum over pairs of nidreg_eval_multi / nidreg_eval_iso_multi: pairs are added in handle order (the gradient sum is floating point)
+namespace {
+struct PairSum {
+  double cost = 0.0, grad[7] = {0, 0, 0, 0, 0, 0, 0};
+  bool all_ok = true;
+  void add(double c, const double* g7 /* null: cost only */) {
+    cost += c;
+    if (g7)
+      for (int k = 0; k < 7; k++) grad[k] += g7[k];
+  }
+  int store(double* cost_out, double* grad7) const {
+    if (cost_out) *cost_out = cost;
+    if (grad7)
+      for (int k = 0; k < 7; k++) grad7[k] = grad[k];
+    return all_ok ? NIDREG_OK : NIDREG_FALSE;
+  }
+};
+}  // namespace
 
 int nidreg_eval_multi(nidreg_handle* const* handles, int n, const double* init_se3, const double* se3, double* cost, double* grad7) {
   if (!handles || n <= 0 || !se3) return fail(NIDREG_ERR_INVALID, "nidreg_eval_multi: bad argument");
@@ -310,20 +325,12 @@ int nidreg_eval_multi(nidreg_handle* const* handles, int n, const double* init_s
       MultiGroup* g = find_or_make_group(handles, n);
       if (g) {
         double costs[kMaxMulti], grads[kMaxMulti * 7];
-        bool all_ok = true;
-        const int rc = group_eval(g, se3, grad7 != nullptr, costs, grad7 ? grads : nullptr, &all_ok);
+        PairSum sum;
+        const int rc = group_eval(g, se3, grad7 != nullptr, costs, grad7 ? grads : nullptr, &sum.all_ok);
         release_group(g);
         if (rc < 0) return rc;
-        double csum = 0.0, gsum[7] = {0, 0, 0, 0, 0, 0, 0};
-        for (int i = 0; i < n; i++) {
-          csum += costs[i];
-          if (grad7)
-            for (int k = 0; k < 7; k++) gsum[k] += grads[7 * i + k];
-        }
-        if (cost) *cost = csum;
-        if (grad7)
-          for (int k = 0; k < 7; k++) grad7[k] = gsum[k];
-        return all_ok ? NIDREG_OK : NIDREG_FALSE;
+        for (int i = 0; i < n; i++) sum.add(costs[i], grad7 ? grads + 7 * i : nullptr);
+        return sum.store(cost, grad7);
       }
     }
   }
@@ -340,29 +347,21 @@ int nidreg_eval_multi(nidreg_handle* const* handles, int n, const double* init_s
   }
   for (int i = 0; i < n; i++) {
     if (handles[i]->set) continue;  // a pair sharded over several GPUs: evaluated through its set below
-    const int rc = eval_launch_first(handles[i], se3, alone[size_t(i)] != 0);  // every pair's (every GPU's) histogram pass is running ...
-    if (rc) return rc;
+    RC_TRY(eval_launch_first(handles[i], se3, alone[size_t(i)] != 0));  // every pair's (every GPU's) histogram pass is running ...
   }
   for (int i = 0; i < n; i++) {
     if (handles[i]->set) continue;
-    const int rc = eval_launch_rest(handles[i], grad7 != nullptr, alone[size_t(i)] != 0);  // ... while the rest is queued behind it
-    if (rc) return rc;
+    RC_TRY(eval_launch_rest(handles[i], grad7 != nullptr, alone[size_t(i)] != 0));  // ... while the rest is queued behind it
   }
-  double csum = 0.0, gsum[7] = {0, 0, 0, 0, 0, 0, 0};
-  bool all_ok = true;
+  PairSum sum;
   for (int i = 0; i < n; i++) {
     double c = 0.0, g[7];
     const int rc = handles[i]->set ? set_eval(handles[i]->set, NIDREG_MODE_SPLINE, se3, &c, grad7 ? g : nullptr) : eval_finish(handles[i], &c, grad7 ? g : nullptr);
     if (rc < 0) return rc;
-    if (rc == NIDREG_FALSE) all_ok = false;
-    csum += c;
-    if (grad7)
-      for (int k = 0; k < 7; k++) gsum[k] += g[k];
+    if (rc == NIDREG_FALSE) sum.all_ok = false;
+    sum.add(c, grad7 ? g : nullptr);
   }
-  if (cost) *cost = csum;
-  if (grad7)
-    for (int k = 0; k < 7; k++) grad7[k] = gsum[k];
-  return all_ok ? NIDREG_OK : NIDREG_FALSE;
+  return sum.store(cost, grad7);
 }
 
 int nidreg_eval_iso_multi(nidreg_handle* const* handles, int n, const double* T, double* cost) {
@@ -372,6 +371,7 @@ int nidreg_eval_iso_multi(nidreg_handle* const* handles, int n, const double* T,
   for (int i = 0; i < n; i++)
     if (handles[i]->rccl_comm) return fail(NIDREG_ERR_INVALID, "nidreg_eval_iso_multi: a handle with a communicator (nidreg_shard_attach_rccl) is a collective of its own: evaluate it with nidreg_eval_iso");
   for (int i = 0; i < n; i++) cohort_check(handles[i]);
+  PairSum sum;  // (all_ok stays true: CostCalculatorNID has no finite check)
   if (handles[0]->mode == NIDREG_MODE_NEAREST && can_group(handles, n)) {  // several pairs on one GPU: one grid per pass
     MultiGroup* g = find_or_make_group(handles, n);
     if (g) {
@@ -379,27 +379,19 @@ int nidreg_eval_iso_multi(nidreg_handle* const* handles, int n, const double* T,
       const int rc = group_eval_iso(g, T, costs);
       release_group(g);
       if (rc < 0) return rc;
-      double csum = 0.0;
-      for (int i = 0; i < n; i++) csum += costs[i];
-      if (cost) *cost = csum;
-      return NIDREG_OK;
+      for (int i = 0; i < n; i++) sum.add(costs[i], nullptr);
+      return sum.store(cost, nullptr);
     }
   }
-  for (int i = 0; i < n; i++) {
-    if (!handles[i]) return fail(NIDREG_ERR_INVALID, "nidreg_eval_iso_multi: null handle");
-    if (handles[i]->set) continue;
-    const int rc = iso_launch(handles[i], T);
-    if (rc) return rc;
-  }
-  double csum = 0.0;
+  for (int i = 0; i < n; i++)
+    if (!handles[i]->set) RC_TRY(iso_launch(handles[i], T));
   for (int i = 0; i < n; i++) {
     double c = 0.0;
     const int rc = handles[i]->set ? set_eval(handles[i]->set, NIDREG_MODE_NEAREST, T, &c, nullptr) : eval_finish(handles[i], &c, nullptr);
     if (rc < 0) return rc;
-    csum += c;
+    sum.add(c, nullptr);
   }
-  if (cost) *cost = csum;
-  return NIDREG_OK;
+  return sum.store(cost, nullptr);
 }
 
 int nidreg_get_hist_fixed(nidreg_handle* h, int64_t* joint, int64_t* inliers, int* frac_bits) {
@@ -415,8 +407,8 @@ int nidreg_get_hist_fixed(nidreg_handle* h, int64_t* joint, int64_t* inliers, in
   // ended, so drain the stream the evaluation really ran on (a multi-pair group's stream is not the handle's)
   HIP_TRY(hipStreamSynchronize(h->last_stream ? h->last_stream : h->stream));
   const int B = h->bins;
-  std::vector<u64> tmp(size_t(h->hist_words));
-  HIP_TRY(hipMemcpy(tmp.data(), h->d_hist, tmp.size() * sizeof(u64), hipMemcpyDeviceToHost));
+  std::vector<u64> tmp(size_t(h->hist.words()));
+  HIP_TRY(hipMemcpy(tmp.data(), h->hist.data(), tmp.size() * sizeof(u64), hipMemcpyDeviceToHost));
   if (joint) {
     // device layout [bin_points][bin_image] -> [bin_image][bin_points]
     if (h->bins_user) {  // bins > 256: the compact bins back to the caller's (every other cell is empty)
@@ -718,12 +710,7 @@ int nidreg_shard_grad(nidreg_handle* h) {
 int nidreg_shard_finish(nidreg_handle* h, double* cost, double* grad7) {
   if (!h) return fail(NIDREG_ERR_INVALID, "nidreg_shard_finish: null handle");
   HIP_TRY(hipSetDevice(h->device));
-  if (!h->d_out_host) HIP_TRY(hipMemcpyAsync(h->h_out, h->d_out, NIDREG_OUT_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (cost) *cost = h->h_out[0];
-  if (grad7)
-    for (int k = 0; k < 7; k++) grad7[k] = h->h_out[1 + k];
-  return h->h_out[8] != 0.0 ? NIDREG_FALSE : NIDREG_OK;
+  return eval_finish_sync(h, !h->d_out_host, cost, grad7);
 }
 
 int nidreg_set_timing(nidreg_handle* h, int enable) {

@@ -10,6 +10,44 @@ int fail(int code, const std::string& msg) {
 }
 }  // namespace nidreg
 
+// ---- the histogram double buffer (nidreg_internal.hpp HistRing)
+hipError_t HistRing::alloc(int64_t words, bool finegrained) {
+  words_ = words;
+  const size_t bytes = size_t(words) * sizeof(u64);
+  for (DeviceBuf& buf : buf_) {
+    const hipError_t e = finegrained ? buf.alloc_finegrained(bytes) : buf.alloc(bytes);
+    if (e != hipSuccess) return e;
+  }
+  d_ = buffer(0);
+  cur_ = 0;
+  cleared_[1] = true;
+  return hipMemset(buffer(1), 0, bytes);
+}
+// With own (double) buffers the previous evaluation's kernels have already zeroed the buffer; a caller-provided buffer or a
+// buffer left dirty by a failed launch is cleared with a memset.
+hipError_t HistRing::begin(hipStream_t stream) {
+  if (own()) {
+    cur_ ^= 1;
+    d_ = buffer(cur_);
+    // The buffer was cleared by the PREVIOUS evaluation's kernels (plain stores of k_entropy / the gradient prologue), and the
+    // host may be here before that kernel has ended: it proceeds on the completion tag.  On the same stream the kernel boundary
+    // orders the clears against this evaluation's atomics; on another stream (a cohort round on a different group's stream, a
+    // caller mixing nidreg_eval and nidreg_eval_multi on one handle) nothing does -- the clears sit in the old kernel's XCD-local
+    // L2 until it ends and could land on top of the new counts.  Rare path: drain the old stream first.
+    if (cleared_[cur_] && clear_stream_ && clear_stream_ != stream) {
+      hipError_t e = hipStreamSynchronize(clear_stream_);
+      if (e != hipSuccess) return e;
+    }
+    if (!cleared_[cur_]) {
+      hipError_t e = hipMemsetAsync(d_, 0, size_t(words_) * sizeof(u64), stream);
+      if (e != hipSuccess) return e;
+    }
+    cleared_[cur_] = false;  // about to be written
+    return hipSuccess;
+  }
+  return hipMemsetAsync(d_, 0, size_t(words_) * sizeof(u64), stream);
+}
+
 namespace nidreg_detail {
 std::atomic<int> g_inflight[NIDREG_MAX_DEVICES];  // evaluations in flight per device (InflightGuard below)
 ResourcePool g_pool[NIDREG_MAX_DEVICES];
@@ -109,7 +147,7 @@ void free_handle(nidreg_handle* h) {
   delete h;
 }
 
-void fill_pass_args(const nidreg_handle* h, PassArgs& a) {
+void fill_pass_args(const nidreg_handle* h, PassArgs& a, double* out_host) {
   std::memset(&a, 0, sizeof(a));
   a.model = h->model;
   a.rec64 = h->rec64;
@@ -132,13 +170,13 @@ void fill_pass_args(const nidreg_handle* h, PassArgs& a) {
   a.magic = fixed_unit_k(h);  // the x-weight constants (bspline_scale)
   a.inv_unit = 1.0 / fixed_unit(h);
   a.cos_fov = std::cos(h->max_fov);
-  a.hist = h->d_hist;
+  a.hist = h->hist.data();
   a.phi_q = h->d_phi_q;
   a.scal = h->d_scal;
   a.partials = h->d_partials;
   for (int k = 0; k < 4; k++) a.q[k] = h->last_q[k];
   a.out = h->d_out;
-  a.out_host = h->d_out_host;
+  a.out_host = result_target(h, out_host);
   a.tag = h->seq;
   a.counter = h->d_counters + 1;
   a.gt_phi_q = h->d_phi_q;
@@ -166,51 +204,25 @@ void pose_from_se3(const double* se3, double* R, double* t) {
   t[1] = se3[5];
   t[2] = se3[6];
 }
-
-// Select the buffer this evaluation accumulates into and make sure it is zero.  With own (double)
-// buffers the previous evaluation's k_entropy has already zeroed it; a caller-provided buffer
-// (ext_hist: the sharded protocol all-reduces it in place) or a buffer left dirty by a failed launch
-// is cleared with a memset.
-hipError_t begin_histogram(nidreg_handle* h, hipStream_t stream) {
-  if (h->own_hist) {
-    h->hist_cur ^= 1;
-    h->d_hist = h->d_hist_buf[h->hist_cur].as<u64>();
-    // The buffer was cleared by the PREVIOUS evaluation's kernels (plain stores of k_entropy / the gradient prologue), and the
-    // host may be here before that kernel has ended: it proceeds on the completion tag.  On the same stream the kernel boundary
-    // orders the clears against this evaluation's atomics; on another stream (a cohort round on a different group's stream, a
-    // caller mixing nidreg_eval and nidreg_eval_multi on one handle) nothing does -- the clears sit in the old kernel's XCD-local
-    // L2 until it ends and could land on top of the new counts.  Rare path: drain the old stream first.
-    if (h->hist_zeroed[h->hist_cur] && h->zero_stream && h->zero_stream != stream) {
-      hipError_t e = hipStreamSynchronize(h->zero_stream);
-      if (e != hipSuccess) return e;
-    }
-    if (!h->hist_zeroed[h->hist_cur]) {
-      hipError_t e = hipMemsetAsync(h->d_hist, 0, size_t(h->hist_words) * sizeof(u64), stream);
-      if (e != hipSuccess) return e;
-    }
-    h->hist_zeroed[h->hist_cur] = false;  // about to be written
-    return hipSuccess;
-  }
-  return hipMemsetAsync(h->d_hist, 0, size_t(h->hist_words) * sizeof(u64), stream);
+void remember_pose(nidreg_handle* h, const double* se3) {
+  for (int k = 0; k < 4; k++) h->last_q[k] = se3[k];
+  pose_from_se3(se3, h->last_R, h->last_t);
 }
-hipError_t begin_histogram(nidreg_handle* h) { return begin_histogram(h, h->stream); }
 
 int launch_hist_spline(nidreg_handle* h, const double* se3, bool alone) {
+  remember_pose(h, se3);
+  HIP_TRY(h->hist.begin(h->stream));
   PassArgs a;
-  fill_pass_args(h, a);
+  fill_pass_args(h, a);  // (after begin: a.hist = this evaluation's buffer)
   a.prio = alone ? 1 : 0;
   if (h->d_chunks_hist) {
     a.chunks = h->d_chunks_hist.as<Chunk>();
     a.nchunks = h->nchunks_hist;
     a.seg = h->seg_hist;
   }
-  pose_from_se3(se3, a.R, a.t);
-  for (int k = 0; k < 4; k++) h->last_q[k] = se3[k];
-  std::memcpy(h->last_R, a.R, sizeof(a.R));
-  std::memcpy(h->last_t, a.t, sizeof(a.t));
-  HIP_TRY(begin_histogram(h));
-  a.hist = h->d_hist;
-  if (h->timing == 1) HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+  std::memcpy(a.R, h->last_R, sizeof(a.R));
+  std::memcpy(a.t, h->last_t, sizeof(a.t));
+  RC_TRY(mark_kernel(h, 1));
   HIP_TRY(launch_spline_hist<double>(a));
   return NIDREG_OK;
 }
@@ -293,40 +305,36 @@ NearestFastArgs nearest_fast_args(const nidreg_handle* h, const double* T) {
 }
 
 int launch_hist_nearest(nidreg_handle* h, const double* T) {
+  HIP_TRY(h->hist.begin(h->stream));
   PassArgs a;
-  fill_pass_args(h, a);
+  fill_pass_args(h, a);  // (after begin: a.hist = this evaluation's buffer)
   a.nfast = nearest_fast_args(h, T);
   for (int k = 0; k < 12; k++) a.iso[k] = T[k];
-  HIP_TRY(begin_histogram(h));
-  a.hist = h->d_hist;
-  if (h->timing == 1) HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+  RC_TRY(mark_kernel(h, 1));
   HIP_TRY(launch_nearest_hist<double>(a));
   return NIDREG_OK;
 }
 
 // tail = false: partials only -- the gradient kernel that follows runs the entropy tail in its prologue (launch_grad with
 // from_partials); tail = true: the last workgroup finalises (cost-only evaluations, the split-phase ABI, empty clouds)
-int launch_entropy(nidreg_handle* h, double tag, bool tail) {
+int launch_entropy(nidreg_handle* h, double tag, bool tail, double* out_host) {
   const double inv_unit = 1.0 / fixed_unit(h);
   hipLaunchKernelGGL(
-    k_entropy<false>, dim3(h->NEB), dim3(kEntropyThreads), 0, h->stream, h->d_hist, h->bins, kEntropyCols, inv_unit, h->d_part_hj, h->d_row_part, h->d_phi_q, h->d_hist_image,
-    h->d_hist_points, h->d_scal, h->d_out, h->d_out_host, tag, h->d_counters, h->own_hist ? h->d_hist_buf[h->hist_cur ^ 1].as<u64>() : nullptr, h->hist_words, tail ? 1 : 0,
-    static_cast<const MultiEntry*>(nullptr), NoMultiDyn());
+    k_entropy<false>, dim3(h->NEB), dim3(kEntropyThreads), 0, h->stream, h->hist.data(), h->bins, kEntropyCols, inv_unit, h->d_part_hj, h->d_row_part, h->d_phi_q, h->d_hist_image,
+    h->d_hist_points, h->d_scal, h->d_out, result_target(h, out_host), tag, h->d_counters, h->hist.idle(), h->hist.words(), tail ? 1 : 0, static_cast<const MultiEntry*>(nullptr),
+    NoMultiDyn());
   HIP_TRY(hipGetLastError());
-  if (h->own_hist) {
-    h->hist_zeroed[h->hist_cur ^ 1] = true;  // zeroed by this k_entropy for the next evaluation
-    h->zero_stream = h->stream;
-  }
+  h->hist.idle_cleared_on(h->stream);  // zeroed by this k_entropy for the next evaluation
   return NIDREG_OK;
 }
 
 // small tables (B <= 32): a cost+Jacobian evaluation launches no entropy kernel, the gradient workgroups sum the table
 // themselves (nid_kernels.hpp kSelfEntropyCells).  NIDREG_NO_SELF_ENTROPY=1: always k_entropy (A/B runs)
-bool grad_sums_table(const nidreg_handle* h) {
+bool grad_sums_table(nidreg_handle* h) {
   if (h->self_entropy < 0) {  // decided at the handle's first cost+Jacobian evaluation
     const char* e = std::getenv("NIDREG_NO_SELF_ENTROPY");
     const bool off = e && *e && *e != '0';
-    const_cast<nidreg_handle*>(h)->self_entropy = (!off && h->mode == NIDREG_MODE_SPLINE && h->GW != 1 && h->bins * h->bins <= kSelfEntropyCells && !h->is_shard && !h->set) ? 1 : 0;
+    h->self_entropy = (!off && h->mode == NIDREG_MODE_SPLINE && h->GW != 1 && h->bins * h->bins <= kSelfEntropyCells && !h->is_shard && !h->set) ? 1 : 0;
   }
   return h->self_entropy == 1;
 }
@@ -337,27 +345,23 @@ hipError_t launch_grad_final(hipStream_t stream, const double* partials, const d
   return hipGetLastError();
 }
 
-int launch_grad(nidreg_handle* h, bool alone, int from_partials) {
+int launch_grad(nidreg_handle* h, bool alone, int from_partials, double* out_host) {
   PassArgs a;
-  fill_pass_args(h, a);
+  fill_pass_args(h, a, out_host);  // (a.hist = the finished histogram; for a shard: its own columns)
   a.prio = alone ? 1 : 0;
   a.gt_from_partials = from_partials;
   if (from_partials == 2) {
-    a.gt_zero_buf = h->own_hist ? h->d_hist_buf[h->hist_cur ^ 1].as<u64>() : nullptr;
-    a.gt_zero_words = h->hist_words;
-    if (h->own_hist) {
-      h->hist_zeroed[h->hist_cur ^ 1] = true;  // zeroed by this evaluation's gradient kernel for the next one
-      h->zero_stream = h->stream;
-    }
+    a.gt_zero_buf = h->hist.idle();
+    a.gt_zero_words = h->hist.words();
+    h->hist.idle_cleared_on(h->stream);  // zeroed by this evaluation's gradient kernel for the next one
   }
-  a.hist = h->d_hist;  // the finished histogram (for a shard: its own columns)
   // same pose as the histogram pass of this evaluation
   std::memcpy(a.R, h->last_R, sizeof(a.R));
   std::memcpy(a.t, h->last_t, sizeof(a.t));
   HIP_TRY(launch_spline_grad<double>(a));
-  if (h->timing == 1) HIP_TRY(hipEventRecord(h->ev[4], h->stream));
+  RC_TRY(mark_kernel(h, 4));
   if (h->nchunks == 0) {  // empty cloud: no gradient workgroups ran, finalise (zeros) stand-alone
-    HIP_TRY(launch_grad_final(h->stream, h->d_partials, h->last_q, h->d_out, h->d_out_host, h->seq));
+    HIP_TRY(launch_grad_final(h->stream, h->d_partials, h->last_q, h->d_out, a.out_host, h->seq));
   }
   return NIDREG_OK;
 }
@@ -368,30 +372,25 @@ int eval_launch_first(nidreg_handle* h, const double* se3, bool alone) {
   if (h->mode != NIDREG_MODE_SPLINE) return fail(NIDREG_ERR_INVALID, "nidreg_eval: handle was created in NEAREST mode");
   HIP_TRY(hipSetDevice(h->device));
   bump_seq(h);
-  if (h->timing) HIP_TRY(hipEventRecord(h->ev[0], h->stream));
-  const int rc = launch_hist_spline(h, se3, alone);
-  if (rc) return rc;
-  if (h->timing == 1) HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-  return NIDREG_OK;
+  RC_TRY(mark_any(h, 0));
+  RC_TRY(launch_hist_spline(h, se3, alone));
+  return mark_kernel(h, 2);
 }
-int eval_launch_rest(nidreg_handle* h, bool want_grad, bool alone) {
+int eval_launch_rest(nidreg_handle* h, bool want_grad, bool alone, double* out_host) {
   HIP_TRY(hipSetDevice(h->device));
   // cost + Jacobian on a non-empty cloud: k_entropy stores its partials and ends; every gradient workgroup runs the tail
   const bool grad_runs_tail = want_grad && h->nchunks > 0;
   const bool no_entropy_kernel = grad_runs_tail && grad_sums_table(h);
-  int rc = no_entropy_kernel ? NIDREG_OK : launch_entropy(h, want_grad ? 0.0 : h->seq, !grad_runs_tail);
-  if (rc) return rc;
-  if (h->timing == 1) HIP_TRY(hipEventRecord(h->ev[3], h->stream));
+  if (!no_entropy_kernel) RC_TRY(launch_entropy(h, want_grad ? 0.0 : h->seq, !grad_runs_tail, out_host));
+  RC_TRY(mark_kernel(h, 3));
   h->ev_grad = want_grad;
   if (want_grad) {
-    rc = launch_grad(h, alone, no_entropy_kernel ? 2 : (grad_runs_tail ? 1 : 0));
-    if (rc) return rc;
-  } else if (h->timing == 1) {
-    HIP_TRY(hipEventRecord(h->ev[4], h->stream));
+    RC_TRY(launch_grad(h, alone, no_entropy_kernel ? 2 : (grad_runs_tail ? 1 : 0), out_host));
+  } else {
+    RC_TRY(mark_kernel(h, 4));
   }
-  if (h->timing) HIP_TRY(hipEventRecord(h->ev[5], h->stream));
-  if (!h->d_out_host) HIP_TRY(hipMemcpyAsync(h->h_out, h->d_out, NIDREG_OUT_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  return NIDREG_OK;
+  RC_TRY(mark_any(h, 5));
+  return result_target(h, out_host) ? NIDREG_OK : copy_results_to_host(h);
 }
 
 // ---- one launch per cost+Jacobian evaluation (nid_fused.hpp) -----------------------------------------------------------------
@@ -405,7 +404,7 @@ void plan_fused(nidreg_handle* h) {
   h->fused = -1;
   const char* off = std::getenv("NIDREG_FUSED");
   if (off && *off == '0') return;
-  if (h->mode != NIDREG_MODE_SPLINE || !grad_sums_table(h) || h->is_shard || h->set || !h->own_hist || h->cohort || h->nchunks <= 0 || h->seg || h->nslots != h->nchunks ||
+  if (h->mode != NIDREG_MODE_SPLINE || !grad_sums_table(h) || h->is_shard || h->set || !h->hist.own() || h->cohort || h->nchunks <= 0 || h->seg || h->nslots != h->nchunks ||
       h->longest_chunk <= 0)
     return;
   if (hipSetDevice(h->device) != hipSuccess) return;
@@ -449,24 +448,22 @@ void fused_give_up(nidreg_handle* h) {
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
   (void)hipMemsetAsync(h->d_counters, 0, 8 * sizeof(unsigned int), h->stream);
-  h->hist_zeroed[0] = h->hist_zeroed[1] = false;  // (whatever the aborted kernel cleared or did not: memset before use)
+  h->hist.distrust();
   (void)hipStreamSynchronize(h->stream);
 }
 int eval_launch_fused(nidreg_handle* h, const double* se3) {
   HIP_TRY(hipSetDevice(h->device));
   bump_seq(h);
-  if (h->timing) HIP_TRY(hipEventRecord(h->ev[0], h->stream));
-  for (int k = 0; k < 4; k++) h->last_q[k] = se3[k];
-  pose_from_se3(se3, h->last_R, h->last_t);
-  HIP_TRY(begin_histogram(h));
+  RC_TRY(mark_any(h, 0));
+  remember_pose(h, se3);
+  HIP_TRY(h->hist.begin(h->stream));
   PassArgs a;
-  fill_pass_args(h, a);  // (after begin_histogram: a.hist = this evaluation's buffer; a.q = the pose's quaternion; a.tag = its sequence number)
+  fill_pass_args(h, a);  // (after begin: a.hist = this evaluation's buffer; a.q = the pose's quaternion; a.tag = its sequence number)
   std::memcpy(a.R, h->last_R, sizeof(a.R));
   std::memcpy(a.t, h->last_t, sizeof(a.t));
-  a.gt_zero_buf = h->d_hist_buf[h->hist_cur ^ 1].as<u64>();
-  a.gt_zero_words = h->hist_words;
-  h->hist_zeroed[h->hist_cur ^ 1] = true;  // cleared by this launch for the next evaluation
-  h->zero_stream = h->stream;
+  a.gt_zero_buf = h->hist.idle();
+  a.gt_zero_words = h->hist.words();
+  h->hist.idle_cleared_on(h->stream);  // cleared by this launch for the next evaluation
   h->fused_arrivals += uint64_t(h->nchunks);
   h->fused_launches += 1;
   const char* tmo = std::getenv("NIDREG_FUSED_TIMEOUT_US");  // (default 5 ms: far beyond any barrier wait of a co-resident grid)
@@ -476,19 +473,24 @@ int eval_launch_fused(nidreg_handle* h, const double* se3) {
   const char* hang = std::getenv("NIDREG_FUSED_TEST_HANG");
   const FusedArgs f{h->d_fused_barrier, h->fused_arrivals + ((hang && *hang == '1') ? 1u : 0u), h->d_fused_barrier + 32, h->fused_launches, timeout_ticks, h->fused_cap, h->fused_full};
   HIP_TRY(launch_spline_fused(a, f));
-  if (h->timing) HIP_TRY(hipEventRecord(h->ev[5], h->stream));
+  RC_TRY(mark_any(h, 5));
   h->ev_grad = true;
   return NIDREG_OK;
 }
 
-int eval_launch(nidreg_handle* h, const double* se3, bool want_grad, bool alone) {
-  const int rc = eval_launch_first(h, se3, alone);
-  if (rc) return rc;
-  return eval_launch_rest(h, want_grad, alone);
+int eval_launch(nidreg_handle* h, const double* se3, bool want_grad, bool alone, double* out_host) {
+  RC_TRY(eval_launch_first(h, se3, alone));
+  return eval_launch_rest(h, want_grad, alone, out_host);
 }
 // `stream` = the stream the evaluation's kernels were queued on (the handle's own, or a multi-pair group's)
 int eval_finish_on(nidreg_handle* h, hipStream_t stream, double* cost, double* grad7) { return eval_finish_block(h, stream, h->h_out, h->seq_bits, h->d_out_host != nullptr, cost, grad7); }
 int eval_finish(nidreg_handle* h, double* cost, double* grad7) { return eval_finish_on(h, h->stream, cost, grad7); }
+// synchronous completion on the handle's own stream (the in-library RCCL route, the split-phase ABI): `copy` = the host block does
+// not hold the results yet (copy_results_to_host)
+int eval_finish_sync(nidreg_handle* h, bool copy, double* cost, double* grad7) {
+  if (copy) RC_TRY(copy_results_to_host(h));
+  return eval_finish_block(h, h->stream, h->h_out, h->seq_bits, false, cost, grad7);
+}
 // `block` = the host-mapped result block the evaluation writes (the handle's own, or a slot of its asynchronous ring) and
 // `seq_bits` the completion tag expected in its last word
 int eval_finish_block(nidreg_handle* h, hipStream_t stream, const double* block, uint64_t seq_bits, bool polled, double* cost, double* grad7) {
@@ -551,35 +553,26 @@ int eval_finish_block(nidreg_handle* h, hipStream_t stream, const double* block,
 int eval_one(nidreg_handle* h, const double* se3, double* cost, double* grad7) {
   InflightGuard guard(h->device);
   if (grad7 && guard.alone && h->async_outstanding == 0 && fused_usable(h)) {
-    int rc = eval_launch_fused(h, se3);
-    if (rc) return rc;
-    rc = eval_finish(h, cost, grad7);
+    RC_TRY(eval_launch_fused(h, se3));
+    const int rc = eval_finish(h, cost, grad7);
     if (rc >= 0) return rc;
     fused_give_up(h);  // ... and fall through to the three kernels
   }
-  const int rc = eval_launch(h, se3, grad7 != nullptr, guard.alone);
-  if (rc) return rc;
+  RC_TRY(eval_launch(h, se3, grad7 != nullptr, guard.alone));
   return eval_finish(h, cost, grad7);
 }
 
-int iso_launch(nidreg_handle* h, const double* T) {
+int iso_launch(nidreg_handle* h, const double* T, double* out_host) {
   if (h->mode != NIDREG_MODE_NEAREST) return fail(NIDREG_ERR_INVALID, "nidreg_eval_iso: handle was created in SPLINE mode");
   HIP_TRY(hipSetDevice(h->device));
   bump_seq(h);
-  if (h->timing) HIP_TRY(hipEventRecord(h->ev[0], h->stream));
-  int rc = launch_hist_nearest(h, T);
-  if (rc) return rc;
-  if (h->timing) HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-  rc = launch_entropy(h, h->seq);
-  if (rc) return rc;
-  if (h->timing) {
-    HIP_TRY(hipEventRecord(h->ev[3], h->stream));
-    HIP_TRY(hipEventRecord(h->ev[4], h->stream));
-    HIP_TRY(hipEventRecord(h->ev[5], h->stream));
-  }
+  RC_TRY(mark_any(h, 0));
+  RC_TRY(launch_hist_nearest(h, T));
+  RC_TRY(mark_any(h, 2));
+  RC_TRY(launch_entropy(h, h->seq, true, out_host));
+  for (int k = 3; k <= 5; k++) RC_TRY(mark_any(h, k));
   h->ev_grad = false;
-  if (!h->d_out_host) HIP_TRY(hipMemcpyAsync(h->h_out, h->d_out, NIDREG_OUT_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  return NIDREG_OK;
+  return result_target(h, out_host) ? NIDREG_OK : copy_results_to_host(h);
 }
 
 // visual_camera_calibration.cpp:149-156: delta = init^-1 * T; reject when |t| > 0.2 m or angle > 2 deg

@@ -73,6 +73,41 @@ const int kNumDist[6] = {5, 4, 4, 0, 1, 8};
 
 }  // namespace
 
+// The fixed-point histogram an evaluation accumulates into, and the one invariant of its double buffer.  With the handle's own
+// two buffers evaluation k accumulates into one and its kernels clear the OTHER, idle one for evaluation k + 1, so no memset sits
+// on the critical path; a caller's buffer (desc.ext_hist: the sharded protocol all-reduces it in place) is cleared by a memset
+// every time.  "Cleared" is a claim about a kernel on a stream: whoever hands idle() to a kernel says so with
+// idle_cleared_on(that kernel's stream), and begin() is the only reader of the claim.
+class NIDREG_HIDDEN HistRing {
+ public:
+  hipError_t alloc(int64_t words, bool finegrained);  // own buffers: [0] current, [1] cleared here (whoever allocates clears the current one)
+  void use(u64* ext, int64_t words) { d_ = ext; words_ = words; }  // the caller's buffer
+  // Select the buffer the evaluation about to be launched on `stream` accumulates into and make sure it is zero (nidreg_core.hip)
+  hipError_t begin(hipStream_t stream);
+  u64* data() const { return d_; }  // histogram of the current / most recent evaluation (accumulation target of pass A)
+  int index() const { return cur_; }
+  int64_t words() const { return words_; }
+  bool own() const { return bool(buf_[0]); }  // data() alternates between buffer(0 / 1) (else: the caller's ext_hist)
+  u64* buffer(int i) const { return buf_[i].as<u64>(); }
+  u64* idle() const { return own() ? buffer(cur_ ^ 1) : nullptr; }  // what the NEXT evaluation accumulates into
+  void idle_cleared_on(hipStream_t stream) {  // a kernel just queued on `stream` zeroes idle()
+    if (!own()) return;
+    cleared_[cur_ ^ 1] = true;
+    clear_stream_ = stream;
+  }
+  void distrust() { cleared_[0] = cleared_[1] = false; }  // whatever an aborted kernel cleared or did not: memset before use
+  void drained(hipStream_t stream) {  // `stream` is idle (and may go away): nothing left to order against
+    if (clear_stream_ == stream) clear_stream_ = nullptr;
+  }
+ private:
+  DeviceBuf buf_[2];  // u64[words_] each
+  u64* d_ = nullptr;
+  int64_t words_ = 0;
+  int cur_ = 0;
+  bool cleared_[2] = {false, false};
+  hipStream_t clear_stream_ = nullptr;  // the stream of the kernel that cleared the idle buffer (begin() orders a launch on another stream behind it)
+};
+
 struct nidreg_handle {
   int device = 0;
   int model = 0, mode = 0, precision = 0, bins = 0;
@@ -108,12 +143,12 @@ struct nidreg_handle {
   // Device memory: these DeviceBuf members own their allocation and free it when free_handle deletes the handle.  Members
   // are destroyed last to first, so they are declared in the REVERSE of the order the allocator gets them back in -- records
   // first, scratch last, the order handles have always been freed in (about the order they were allocated in).  The plain
-  // pointers further down (d_hist, d_out, d_part_hj ... d_counters, d_fused_barrier) are what the kernels are handed: views into
+  // pointers further down (d_out, d_part_hj ... d_counters, d_fused_barrier) are what the kernels are handed: views into
   // an owner or a caller's buffer (desc.ext_hist / ext_out), filled at creation.
   DeviceBuf d_scratch;        // ONE allocation carved into the per-evaluation scratch below (zeroed at creation)
   DeviceBuf d_out_buf;        // double[NIDREG_OUT_DOUBLES] behind d_out (own_out)
   DeviceBuf d_shard_tab;      // device copy of this shard's ShardTable (peer flag / gather blocks, owned columns)
-  DeviceBuf d_hist_buf[2];    // u64[hist_words] each: the histogram double buffer (own_hist)
+  HistRing hist;              // the histogram double buffer (or the caller's ext_hist)
   DeviceBuf d_img;            // uint8_t padded bin image
   DeviceBuf d_gend;           // uint32_t[NG] end offsets of the column groups among the records (nid_kernels.hpp Segments)
   DeviceBuf d_eq_tab;         // double[2 (eq_kmax + 1) + eq_jmax + 1]: NEAREST, equirectangular (below)
@@ -121,7 +156,6 @@ struct nidreg_handle {
   DeviceBuf d_chunks_hist;    // Chunk[chunks_hist_cap]
   DeviceBuf d_chunks;         // Chunk[chunks_cap]
   DeviceBuf d_pts;            // Rec64 / Rec32 records
-  u64* d_hist = nullptr;      // histogram of the current / most recent evaluation (accumulation target of pass A)
   // a shard of a ShardSet owns a range of histogram COLUMN GROUPS: it holds the points of those columns only, and its
   // histogram is the pair's histogram restricted to them (the other columns stay zero)
   struct ShardSet* set = nullptr;  // non-NULL on the leader (shard 0) of a set: nidreg_eval* fan out over the shards
@@ -133,12 +167,6 @@ struct nidreg_handle {
   bool rccl_owned = false;
   int col_lo = 0, col_hi = 0;         // owned histogram columns
   size_t img_bytes = 0;
-  // double buffering of the histogram (own buffers only): evaluation k accumulates into one buffer and
-  // its k_entropy zeroes the OTHER one for evaluation k + 1, so no memset sits on the critical path
-  bool hist_zeroed[2] = {false, false};
-  hipStream_t zero_stream = nullptr;  // the stream of the kernel that cleared the idle buffer (begin_histogram orders a launch on another stream behind it)
-  int hist_cur = 0;
-  bool own_hist = false;  // d_hist alternates between d_hist_buf[0 / 1] (else: the caller's ext_hist)
   double* d_out = nullptr;
   bool own_out = false;  // d_out is d_out_buf (else: the caller's ext_out)
   long long* d_part_hj = nullptr;  // fixed-point entropy partials (nid_kernels.hpp ent_fixed)
@@ -170,7 +198,6 @@ struct nidreg_handle {
                             // submit on handles whose submit evaluates synchronously (shards bump the leader's seq themselves)
 
   size_t lds_hist = 0, lds_grad = 0, lds_entropy = 0;
-  int64_t hist_words = 0;
   std::vector<int64_t> gcount;  // record offsets of the column groups (host copy: multi-pair groups build their chunk tables from it)
   int num_cus = 256, per_cu_grad = 4, per_cu_hist = 2;
 
@@ -189,6 +216,7 @@ struct nidreg_handle {
   int timing = 0;  // 1: per-kernel events (three-kernel path), 2: events around whichever path runs
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   bool ev_grad = false;
+  // pose of the SPLINE evaluation in flight (remember_pose): the gradient pass runs at the pose of the histogram pass
   double last_q[4] = {0, 0, 0, 1};
   double last_R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   double last_t[3] = {0, 0, 0};
@@ -422,30 +450,32 @@ hipError_t pool_host_block(int device, bool ring, size_t bytes, void** out);
 void unpool_host_block(int device, bool ring, void* p);
 void pool_release(int device);
 void free_handle(nidreg_handle* h);
-void fill_pass_args(const nidreg_handle* h, PassArgs& a);
+// `out_host` of the launch helpers = the host-mapped block the evaluation writes its results and completion tag into: the
+// handle's own (the default) or a slot of its asynchronous ring (result_target)
+void fill_pass_args(const nidreg_handle* h, PassArgs& a, double* out_host = nullptr);
 void pose_from_se3(const double* se3, double* R, double* t);
-hipError_t begin_histogram(nidreg_handle* h, hipStream_t stream);
-hipError_t begin_histogram(nidreg_handle* h);
+void remember_pose(nidreg_handle* h, const double* se3);
 int launch_hist_spline(nidreg_handle* h, const double* se3, bool alone = false);
 NearestFastArgs nearest_fast_args(const nidreg_handle* h, const double* T);
 int launch_hist_nearest(nidreg_handle* h, const double* T);
-int launch_entropy(nidreg_handle* h, double tag, bool tail = true);
-bool grad_sums_table(const nidreg_handle* h);
-int launch_grad(nidreg_handle* h, bool alone = false, int from_partials = 0);
+int launch_entropy(nidreg_handle* h, double tag, bool tail = true, double* out_host = nullptr);
+bool grad_sums_table(nidreg_handle* h);
+int launch_grad(nidreg_handle* h, bool alone = false, int from_partials = 0, double* out_host = nullptr);
 hipError_t launch_grad_final(hipStream_t stream, const double* partials, const double* q4, double* out, double* out_host, double tag);
 int eval_launch_first(nidreg_handle* h, const double* se3, bool alone = false);
-int eval_launch_rest(nidreg_handle* h, bool want_grad, bool alone = false);
+int eval_launch_rest(nidreg_handle* h, bool want_grad, bool alone = false, double* out_host = nullptr);
 void plan_fused(nidreg_handle* h);
 bool fused_planned(nidreg_handle* h);
 bool fused_usable(nidreg_handle* h);
 void fused_give_up(nidreg_handle* h);
 int eval_launch_fused(nidreg_handle* h, const double* se3);
-int eval_launch(nidreg_handle* h, const double* se3, bool want_grad, bool alone = false);
+int eval_launch(nidreg_handle* h, const double* se3, bool want_grad, bool alone = false, double* out_host = nullptr);
 int eval_finish_on(nidreg_handle* h, hipStream_t stream, double* cost, double* grad7);
 int eval_finish(nidreg_handle* h, double* cost, double* grad7);
 int eval_finish_block(nidreg_handle* h, hipStream_t stream, const double* block, uint64_t seq_bits, bool polled, double* cost, double* grad7);
+int eval_finish_sync(nidreg_handle* h, bool copy, double* cost, double* grad7);
 int eval_one(nidreg_handle* h, const double* se3, double* cost, double* grad7);
-int iso_launch(nidreg_handle* h, const double* T);
+int iso_launch(nidreg_handle* h, const double* T, double* out_host = nullptr);
 bool trust_gate_ok(const double* init, const double* se3);
 int64_t fill_chunks(const int64_t* gcount, int NG, int64_t C, int64_t overhead, int max_segs, int pair, std::vector<Chunk>* out, int64_t* nslots_out = nullptr);
 int64_t best_bound(const int64_t* gcount, int NG, int64_t target, int64_t overhead, int max_segs, int64_t N, int64_t nonempty, int64_t* nchunks_out);
@@ -510,6 +540,21 @@ inline void bump_seq(nidreg_handle* h) {
   h->seq += 1.0;
   std::memcpy(&h->seq_bits, &h->seq, sizeof(h->seq_bits));
 }
+NIDREG_HIDDEN inline double* result_target(const nidreg_handle* h, double* out_host) { return out_host ? out_host : h->d_out_host; }
+// results that are not host-mapped (desc.ext_out) or that a collective changed on the device: their copy into the handle's host
+// block, queued behind the evaluation
+NIDREG_HIDDEN inline int copy_results_to_host(nidreg_handle* h) {
+  HIP_TRY(hipMemcpyAsync(h->h_out, h->d_out, NIDREG_OUT_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  return NIDREG_OK;
+}
+#define RC_TRY(expr) do { if (const int _rc = (expr)) return _rc; } while (0)
+// timing marks (nidreg_set_timing): event k on the handle's stream.  mark_any: timing of either kind; mark_kernel: per-kernel
+// timing (1) only -- the marks between the kernels of the three-kernel route
+NIDREG_HIDDEN inline int mark_any(nidreg_handle* h, int k) {
+  if (h->timing) HIP_TRY(hipEventRecord(h->ev[k], h->stream));
+  return NIDREG_OK;
+}
+NIDREG_HIDDEN inline int mark_kernel(nidreg_handle* h, int k) { return h->timing == 1 ? mark_any(h, k) : NIDREG_OK; }
 // every evaluation entry point, before it reads the handle's tables
 inline void cohort_check(nidreg_handle* h) {
   if (h->cohort && !h->cohort->sealed.load(std::memory_order_acquire)) cohort_seal(h->cohort);

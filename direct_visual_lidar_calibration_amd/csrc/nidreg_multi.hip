@@ -14,7 +14,7 @@ void free_group(MultiGroup* g) {
   for (nidreg_handle* m : g->hs)  // (ADVICE r3 made the getters drain the stream of the last evaluation: never a freed group's)
   {
     if (m->last_stream == g->stream) m->last_stream = m->stream;
-    if (m->zero_stream == g->stream) m->zero_stream = nullptr;  // drained above: nothing left to order against
+    m->hist.drained(g->stream);
   }
   if (g->stream) unpool_stream(g->device, g->stream);  // (synchronised above)
   delete g;  // (frees the tables last, device current and stream drained: the order free_handle's header explains)
@@ -49,7 +49,7 @@ void drop_groups_of(const nidreg_handle* h) {
 bool groupable(const nidreg_handle* a, const nidreg_handle* b) {
   return a->device == b->device && a->model == b->model && a->mode == b->mode && a->max_fov == b->max_fov && a->precision == b->precision && a->bins == b->bins &&
          a->W == b->W && a->H == b->H && a->pitch == b->pitch && a->GW == b->GW && a->cshift == b->cshift && a->wide == b->wide && a->rec64 == b->rec64 &&
-         std::memcmp(a->intr, b->intr, sizeof(a->intr)) == 0 && std::memcmp(a->dist, b->dist, sizeof(a->dist)) == 0 && a->own_hist && b->own_hist && a->d_out_host && b->d_out_host &&
+         std::memcmp(a->intr, b->intr, sizeof(a->intr)) == 0 && std::memcmp(a->dist, b->dist, sizeof(a->dist)) == 0 && a->hist.own() && b->hist.own() && a->d_out_host && b->d_out_host &&
          !a->set && !b->set && !a->is_shard && !b->is_shard && !a->timing && !b->timing;
 }
 
@@ -138,7 +138,7 @@ void cohort_seal(Cohort* c) {
   if (c->device >= 0 && c->device < NIDREG_MAX_DEVICES && g_open_cohort[c->device] == c) g_open_cohort[c->device] = nullptr;
 }
 void cohort_join(nidreg_handle* h) {
-  if (!cohorts_enabled() || h->mode != NIDREG_MODE_SPLINE || h->set || h->is_shard || !h->own_hist || !h->d_out_host || !h->own_stream || h->device < 0 || h->device >= NIDREG_MAX_DEVICES) return;
+  if (!cohorts_enabled() || h->mode != NIDREG_MODE_SPLINE || h->set || h->is_shard || !h->hist.own() || !h->d_out_host || !h->own_stream || h->device < 0 || h->device >= NIDREG_MAX_DEVICES) return;
   Cohort* to_seal = nullptr;
   {
     std::lock_guard<std::mutex> gl(g_cohort_mu);
@@ -239,8 +239,8 @@ MultiGroup* find_or_make_group(nidreg_handle* const* handles, int n) {
     e.pts = h->d_pts.as<void>();
     e.gend = h->d_gend.as<uint32_t>();
     e.img = h->d_img.as<uint8_t>();
-    e.hist_buf[0] = h->d_hist_buf[0].as<u64>();
-    e.hist_buf[1] = h->d_hist_buf[1].as<u64>();
+    e.hist_buf[0] = h->hist.buffer(0);
+    e.hist_buf[1] = h->hist.buffer(1);
     e.k16 = fixed_unit_k(h);
     e.inv_unit = 1.0 / fixed_unit(h);
     e.part_hj = h->d_part_hj;
@@ -253,7 +253,7 @@ MultiGroup* find_or_make_group(nidreg_handle* const* handles, int n) {
     e.out = h->d_out;
     e.out_host = h->d_out_host;
     e.counters = h->d_counters;
-    e.zero_words = h->hist_words;
+    e.zero_words = h->hist.words();
     e.nslots = int(pair_slots);
     e.nchunks = int(pair_grad[size_t(i)].size());
     if (e.nslots > h->partials_cap) {  // the pair's partial buffer (12 doubles per slot) was sized at its creation
@@ -301,6 +301,36 @@ MultiGroup* find_or_make_group(nidreg_handle* const* handles, int n) {
   return g;
 }
 
+// what the two evaluations of a group share.  Every pair starts an evaluation on the group's stream: its sequence number, its
+// cleared histogram buffer, its slot of the launch's MultiDyn (se3: the SPLINE pose, null for NEAREST)
+static int group_begin(MultiGroup* g, MultiDyn& dyn, bool want_grad, const double* se3) {
+  for (size_t i = 0; i < g->hs.size(); i++) {
+    nidreg_handle* h = g->hs[i];
+    bump_seq(h);
+    HIP_TRY(h->hist.begin(g->stream));
+    dyn.cur[i] = h->hist.index();
+    dyn.tag[i] = h->seq;
+    h->last_stream = g->stream;
+    if (se3) remember_pose(h, se3);
+    h->ev_grad = want_grad;
+  }
+  return NIDREG_OK;
+}
+// NEB workgroups per pair; everything a pair's workgroups need comes from its MultiEntry
+static int launch_entropy_group(MultiGroup* g, const MultiDyn& dyn) {
+  const nidreg_handle* h0 = g->hs[0];
+  hipLaunchKernelGGL(
+    k_entropy<true>, dim3(h0->NEB * int(g->hs.size())), dim3(kEntropyThreads), 0, g->stream, static_cast<u64*>(nullptr), h0->bins, kEntropyCols, 0.0, static_cast<long long*>(nullptr),
+    static_cast<u64*>(nullptr), static_cast<double*>(nullptr), static_cast<double*>(nullptr), static_cast<double*>(nullptr), static_cast<EntropyScalars*>(nullptr), static_cast<double*>(nullptr),
+    static_cast<double*>(nullptr), 0.0, static_cast<unsigned int*>(nullptr), static_cast<u64*>(nullptr), 0ll, 1, g->d_table.as<const MultiEntry>(), dyn);
+  HIP_TRY(hipGetLastError());
+  return NIDREG_OK;
+}
+// the group's kernels (k_entropy<true>, or the gradient workgroups of small tables) zero every pair's idle buffer
+static void group_idle_cleared(MultiGroup* g) {
+  for (nidreg_handle* h : g->hs) h->hist.idle_cleared_on(g->stream);
+}
+
 // one evaluation of a group: three launches for all pairs, then every pair's completion tag
 int group_eval(MultiGroup* g, const double* se3, bool want_grad, double* costs, double* grads /* n x 7 or null */, bool* all_ok, int* rcs) {
   const int n = int(g->hs.size());
@@ -316,18 +346,7 @@ int group_eval(MultiGroup* g, const double* se3, bool want_grad, double* costs, 
   a.prio = guard.alone ? 1 : 0;
   pose_from_se3(se3, a.R, a.t);
   for (int k = 0; k < 4; k++) a.q[k] = se3[k];
-  for (int i = 0; i < n; i++) {
-    nidreg_handle* h = g->hs[size_t(i)];
-    bump_seq(h);
-    HIP_TRY(begin_histogram(h, g->stream));
-    a.dyn.cur[i] = h->hist_cur;
-    a.dyn.tag[i] = h->seq;
-    h->last_stream = g->stream;
-    for (int k = 0; k < 4; k++) h->last_q[k] = se3[k];
-    std::memcpy(h->last_R, a.R, sizeof(a.R));
-    std::memcpy(h->last_t, a.t, sizeof(a.t));
-    h->ev_grad = want_grad;
-    }
+  RC_TRY(group_begin(g, a.dyn, want_grad, se3));
   // pass A
   a.chunks = (h0->wide ? g->d_chunks_hist : g->d_chunks).as<Chunk>();
   a.nchunks = h0->wide ? g->nchunks_hist : g->nchunks;
@@ -336,18 +355,9 @@ int group_eval(MultiGroup* g, const double* se3, bool want_grad, double* costs, 
   // entropy: NEB workgroups per pair -- none for small tables when every pair has gradient workgroups (they sum the table
   // themselves and clear the next evaluation's buffers, grad_sums_table)
   bool no_entropy_kernel = want_grad && grad_sums_table(h0);
-  for (int i = 0; i < n && no_entropy_kernel; i++) no_entropy_kernel = g->hs[size_t(i)]->num_points > 0 && g->hs[size_t(i)]->own_hist;
-  if (!no_entropy_kernel) {
-    hipLaunchKernelGGL(
-      k_entropy<true>, dim3(h0->NEB * n), dim3(kEntropyThreads), 0, g->stream, static_cast<u64*>(nullptr), h0->bins, kEntropyCols, 0.0, static_cast<long long*>(nullptr),
-      static_cast<u64*>(nullptr), static_cast<double*>(nullptr), static_cast<double*>(nullptr), static_cast<double*>(nullptr), static_cast<EntropyScalars*>(nullptr), static_cast<double*>(nullptr),
-      static_cast<double*>(nullptr), 0.0, static_cast<unsigned int*>(nullptr), static_cast<u64*>(nullptr), 0ll, 1, g->d_table.as<const MultiEntry>(), a.dyn);
-    HIP_TRY(hipGetLastError());
-  }
-  for (int i = 0; i < n; i++) {
-    g->hs[size_t(i)]->hist_zeroed[g->hs[size_t(i)]->hist_cur ^ 1] = true;
-    g->hs[size_t(i)]->zero_stream = g->stream;
-  }
+  for (int i = 0; i < n && no_entropy_kernel; i++) no_entropy_kernel = g->hs[size_t(i)]->num_points > 0 && g->hs[size_t(i)]->hist.own();
+  if (!no_entropy_kernel) RC_TRY(launch_entropy_group(g, a.dyn));
+  group_idle_cleared(g);
   // pass B (k_entropy<true> ran without its tail for every pair that has gradient workgroups: they run it)
   if (want_grad) {
     a.chunks = g->d_chunks.as<Chunk>();
@@ -519,28 +529,13 @@ int group_eval_iso(MultiGroup* g, const double* T, double* costs) {
   a.dyn.neb = h0->NEB;
   for (int k = 0; k < 12; k++) a.iso[k] = T[k];
   a.nfast = nearest_fast_args(h0, T);
-  for (int i = 0; i < n; i++) {
-    nidreg_handle* h = g->hs[size_t(i)];
-    bump_seq(h);
-    HIP_TRY(begin_histogram(h, g->stream));
-    a.dyn.cur[i] = h->hist_cur;
-    a.dyn.tag[i] = h->seq;
-    h->last_stream = g->stream;
-    h->ev_grad = false;
-  }
+  RC_TRY(group_begin(g, a.dyn, false, nullptr));
   a.chunks = g->d_chunks.as<Chunk>();
   a.nchunks = g->nchunks;
   a.seg = g->seg;
   HIP_TRY(launch_nearest_hist<double>(a));
-  hipLaunchKernelGGL(
-    k_entropy<true>, dim3(h0->NEB * n), dim3(kEntropyThreads), 0, g->stream, static_cast<u64*>(nullptr), h0->bins, kEntropyCols, 0.0, static_cast<long long*>(nullptr),
-    static_cast<u64*>(nullptr), static_cast<double*>(nullptr), static_cast<double*>(nullptr), static_cast<double*>(nullptr), static_cast<EntropyScalars*>(nullptr), static_cast<double*>(nullptr),
-    static_cast<double*>(nullptr), 0.0, static_cast<unsigned int*>(nullptr), static_cast<u64*>(nullptr), 0ll, 1, g->d_table.as<const MultiEntry>(), a.dyn);
-  HIP_TRY(hipGetLastError());
-  for (int i = 0; i < n; i++) {
-    g->hs[size_t(i)]->hist_zeroed[g->hs[size_t(i)]->hist_cur ^ 1] = true;
-    g->hs[size_t(i)]->zero_stream = g->stream;
-  }
+  RC_TRY(launch_entropy_group(g, a.dyn));
+  group_idle_cleared(g);
   for (int i = 0; i < n; i++) {
     const int rc = eval_finish_on(g->hs[size_t(i)], g->stream, costs + i, nullptr);
     if (rc < 0) return rc;

@@ -530,8 +530,7 @@ int build_equirect_tables(nidreg_handle* h) {
 // ---- per-evaluation state: the stream, the histogram double buffer, the result block, the scratch, the host block, the events
 int alloc_eval_state(nidreg_handle* h, const nidreg_desc& d, bool shard) {
   const int B = h->bins;
-  h->hist_words = nidreg_hist_words(B);
-  const size_t hist_bytes = size_t(h->hist_words) * sizeof(u64);
+  const int64_t hist_words = nidreg_hist_words(B);
   if (d.ext_stream || (d.flags & NIDREG_FLAG_EXT_STREAM)) {
     h->stream = static_cast<hipStream_t>(d.ext_stream);
   } else {
@@ -539,16 +538,11 @@ int alloc_eval_state(nidreg_handle* h, const nidreg_desc& d, bool shard) {
     h->own_stream = true;
   }
   if (d.ext_hist) {
-    h->d_hist = static_cast<u64*>(d.ext_hist);
+    h->hist.use(static_cast<u64*>(d.ext_hist), hist_words);
   } else {
     // a shard's two buffers are replicas of the WHOLE pair's histogram: the owners of the other columns store into them from
     // their own devices (nid_kernels.hpp k_entropy_repl) -- fine-grained (coherent) device memory, mapped into every peer
-    for (DeviceBuf& buf : h->d_hist_buf) HIP_TRY(shard ? buf.alloc_finegrained(hist_bytes) : buf.alloc(hist_bytes));
-    HIP_TRY(hipMemset(h->d_hist_buf[1].as<void>(), 0, hist_bytes));
-    h->d_hist = h->d_hist_buf[0].as<u64>();
-    h->hist_cur = 0;
-    h->hist_zeroed[1] = true;  // [0] is zeroed below and read by nidreg_get_hist before the first evaluation
-    h->own_hist = true;
+    HIP_TRY(h->hist.alloc(hist_words, shard));  // ([0] is zeroed below and read by nidreg_get_hist before the first evaluation)
   }
   if (d.ext_out) {
     h->d_out = static_cast<double*>(d.ext_out);
@@ -558,7 +552,7 @@ int alloc_eval_state(nidreg_handle* h, const nidreg_desc& d, bool shard) {
     h->own_out = true;
   }
   HIP_TRY(hipMemset(h->d_out, 0, NIDREG_OUT_DOUBLES * sizeof(double)));
-  HIP_TRY(hipMemset(h->d_hist, 0, hist_bytes));
+  HIP_TRY(hipMemset(h->hist.data(), 0, size_t(hist_words) * sizeof(u64)));
   {
     // one allocation, carved (256-byte aligned) and zeroed: nidreg_get_hist before the first evaluation then
     // reads zeros, not uninitialised memory

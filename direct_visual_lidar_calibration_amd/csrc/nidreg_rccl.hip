@@ -51,7 +51,7 @@ void rccl_release(nidreg_handle* h) {
 int rccl_check_agreement(nidreg_handle* h, ncclComm_t comm, const char* who) {
   RcclApi* api = rccl_api();
   const int kN = 5;
-  long long v[2 * kN] = {h->frac_bits, h->bins, (long long)h->hist_words, h->mode, h->bins_user};
+  long long v[2 * kN] = {h->frac_bits, h->bins, (long long)h->hist.words(), h->mode, h->bins_user};
   for (int k = 0; k < kN; k++) v[kN + k] = -v[k];
   DeviceBuf buf;
   HIP_TRY(buf.alloc(sizeof(v)));
@@ -75,7 +75,7 @@ int rccl_check_agreement(nidreg_handle* h, ncclComm_t comm, const char* who) {
 int rccl_attachable(const nidreg_handle* h, const char* who) {
   if (!h) return fail(NIDREG_ERR_INVALID, std::string(who) + ": null handle");
   if (h->set || h->is_shard) return fail(NIDREG_ERR_INVALID, std::string(who) + ": the handle is already sharded inside the library (desc.device_ids / NIDREG_DEVICES)");
-  if (!h->own_hist || !h->own_out) return fail(NIDREG_ERR_INVALID, std::string(who) + ": the handle must own its histogram and result buffers (no ext_hist / ext_out)");
+  if (!h->hist.own() || !h->own_out) return fail(NIDREG_ERR_INVALID, std::string(who) + ": the handle must own its histogram and result buffers (no ext_hist / ext_out)");
   if (h->async_outstanding != 0) return fail(NIDREG_ERR_INVALID, std::string(who) + ": collect the handle's outstanding tickets first");
   return NIDREG_OK;
 }
@@ -90,37 +90,28 @@ int rccl_eval(nidreg_handle* h, int mode, const double* pose, double* cost, doub
   InflightGuard guard(h->device);
   bump_seq(h);
   const bool grad = mode == NIDREG_MODE_SPLINE && grad7 != nullptr;
-  if (h->timing) HIP_TRY(hipEventRecord(h->ev[0], h->stream));
+  RC_TRY(mark_any(h, 0));
   if (h->num_points == 0) {  // a rank without points launches no histogram kernel: its (cleared) buffer still takes part in the sum
-    HIP_TRY(begin_histogram(h));
-    if (h->timing == 1) HIP_TRY(hipEventRecord(h->ev[1], h->stream));  // (the marker launch_hist_* would have recorded: nidreg_get_timing reads it)
-    if (mode == NIDREG_MODE_SPLINE) {
-      for (int k = 0; k < 4; k++) h->last_q[k] = pose[k];
-      pose_from_se3(pose, h->last_R, h->last_t);
-    }
+    HIP_TRY(h->hist.begin(h->stream));
+    RC_TRY(mark_kernel(h, 1));  // (the marker launch_hist_* would have recorded: nidreg_get_timing reads it)
+    if (mode == NIDREG_MODE_SPLINE) remember_pose(h, pose);
   } else {
-    const int rc = mode == NIDREG_MODE_SPLINE ? launch_hist_spline(h, pose, guard.alone) : launch_hist_nearest(h, pose);
-    if (rc) return rc;
+    RC_TRY(mode == NIDREG_MODE_SPLINE ? launch_hist_spline(h, pose, guard.alone) : launch_hist_nearest(h, pose));
   }
-  if (h->timing) HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-  RCCL_TRY(api->AllReduce(h->d_hist, h->d_hist, size_t(h->hist_words), ncclInt64, ncclSum, comm, h->stream));
-  int rc = launch_entropy(h, 0.0, true);
-  if (rc) return rc;
-  if (h->timing) HIP_TRY(hipEventRecord(h->ev[3], h->stream));
+  RC_TRY(mark_any(h, 2));
+  u64* const hist = h->hist.data();
+  RCCL_TRY(api->AllReduce(hist, hist, size_t(h->hist.words()), ncclInt64, ncclSum, comm, h->stream));
+  RC_TRY(launch_entropy(h, 0.0, true));
+  RC_TRY(mark_any(h, 3));
   if (grad) {
-    rc = launch_grad(h, guard.alone, 0);
-    if (rc) return rc;
+    RC_TRY(launch_grad(h, guard.alone, 0));
     RCCL_TRY(api->AllReduce(h->d_out + 1, h->d_out + 1, 7, ncclFloat64, ncclSum, comm, h->stream));
-  } else if (h->timing) {
-    HIP_TRY(hipEventRecord(h->ev[4], h->stream));
+  } else {
+    RC_TRY(mark_any(h, 4));
   }
-  if (h->timing) HIP_TRY(hipEventRecord(h->ev[5], h->stream));
+  RC_TRY(mark_any(h, 5));
   h->ev_grad = grad;
-  HIP_TRY(hipMemcpyAsync(h->h_out, h->d_out, NIDREG_OUT_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (cost) *cost = h->h_out[0];
-  if (grad)
-    for (int k = 0; k < 7; k++) grad7[k] = h->h_out[1 + k];
-  return h->h_out[8] != 0.0 ? NIDREG_FALSE : NIDREG_OK;
+  // (the results are host-mapped, but the all-reduce changed the gradient on the device after the kernels wrote it: always copied)
+  return eval_finish_sync(h, true, cost, grad ? grad7 : nullptr);
 }
 }  // namespace nidreg_detail

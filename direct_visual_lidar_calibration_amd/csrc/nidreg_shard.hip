@@ -48,44 +48,36 @@ int shard_launch_phase(ShardSet* set, int g, int phase, bool alone) {
   if (phase == 0) {
     bump_seq(h);
     h->h_out[10] = 0.0;
-    if (h->timing) HIP_TRY(hipEventRecord(h->ev[0], h->stream));
+    RC_TRY(mark_any(h, 0));
     if (h->nchunks == 0) {  // no points in this shard's columns: no histogram kernel runs, its columns of the replica stay zero
-      HIP_TRY(begin_histogram(h));
-      if (set->job_mode == NIDREG_MODE_SPLINE) {
-        for (int k = 0; k < 4; k++) h->last_q[k] = set->job_pose[k];
-        pose_from_se3(set->job_pose, h->last_R, h->last_t);
-      }
+      HIP_TRY(h->hist.begin(h->stream));
+      if (set->job_mode == NIDREG_MODE_SPLINE) remember_pose(h, set->job_pose);
     } else {
-      const int rc = set->job_mode == NIDREG_MODE_SPLINE ? launch_hist_spline(h, set->job_pose, alone) : launch_hist_nearest(h, set->job_pose);
-      if (rc) return rc;
+      RC_TRY(set->job_mode == NIDREG_MODE_SPLINE ? launch_hist_spline(h, set->job_pose, alone) : launch_hist_nearest(h, set->job_pose));
     }
-    if (h->timing) HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-    return NIDREG_OK;
+    return mark_any(h, 2);
   }
   if (phase == 1 || phase == 2) {
     const int role = set->colocated ? (phase == 1 ? SHARD_PUSH : SHARD_REDUCE) : (SHARD_PUSH | SHARD_REDUCE);
     if (phase == 2 && !set->colocated) return NIDREG_OK;
     const bool reduces = (role & SHARD_REDUCE) != 0;
-    hipLaunchKernelGGL(k_entropy_repl, dim3(set->nblocks), dim3(kEntropyThreads), 0, h->stream, h->d_hist, h->bins, 1.0 / fixed_unit(h), h->d_shard_tab.as<ShardTable>(), set->seq, h->hist_cur, role, h->d_phi_q,
-                       h->d_hist_image, h->d_hist_points, h->d_scal, h->d_out, h->d_out_host, grad ? 0.0 : h->seq, h->d_counters, reduces ? h->d_hist_buf[h->hist_cur ^ 1].as<u64>() : nullptr, h->hist_words,
+    hipLaunchKernelGGL(k_entropy_repl, dim3(set->nblocks), dim3(kEntropyThreads), 0, h->stream, h->hist.data(), h->bins, 1.0 / fixed_unit(h), h->d_shard_tab.as<ShardTable>(), set->seq, h->hist.index(), role, h->d_phi_q,
+                       h->d_hist_image, h->d_hist_points, h->d_scal, h->d_out, h->d_out_host, grad ? 0.0 : h->seq, h->d_counters, reduces ? h->hist.idle() : nullptr, h->hist.words(),
                        grad_runs_tail ? 0 : 1, h->d_out + 10, h->d_out_host ? h->d_out_host + 10 : nullptr, set->timeout_ticks);
     HIP_TRY(hipGetLastError());
     if (reduces) {
-      h->hist_zeroed[h->hist_cur ^ 1] = true;
-      h->zero_stream = h->stream;
-      if (h->timing) HIP_TRY(hipEventRecord(h->ev[3], h->stream));
+      h->hist.idle_cleared_on(h->stream);
+      RC_TRY(mark_any(h, 3));
     }
     return NIDREG_OK;
   }
   if (grad) {
-    const int rc = launch_grad(h, alone, grad_runs_tail ? 1 : 0);  // records ev[4]; an empty shard finalises zeros stand-alone
-    if (rc) return rc;
-  } else if (h->timing) {
-    HIP_TRY(hipEventRecord(h->ev[4], h->stream));
+    RC_TRY(launch_grad(h, alone, grad_runs_tail ? 1 : 0));  // records ev[4]; an empty shard finalises zeros stand-alone
+  } else {
+    RC_TRY(mark_any(h, 4));
   }
-  if (h->timing) HIP_TRY(hipEventRecord(h->ev[5], h->stream));
   h->ev_grad = grad;
-  return NIDREG_OK;
+  return mark_any(h, 5);
 }
 
 int shard_finish(ShardSet* set, int g) {
@@ -397,8 +389,8 @@ int create_sharded(const nidreg_desc* d, const nidreg_cloud* cloud, const double
     for (int p = 0; p < n; p++) {
       tab.flags[p] = set->flags[size_t(p)].as<u64>();
       tab.gather[p] = set->gather[size_t(p)].as<u64>();
-      tab.hist[p][0] = set->shards[size_t(p)]->d_hist_buf[0].as<u64>();
-      tab.hist[p][1] = set->shards[size_t(p)]->d_hist_buf[1].as<u64>();
+      tab.hist[p][0] = set->shards[size_t(p)]->hist.buffer(0);
+      tab.hist[p][1] = set->shards[size_t(p)]->hist.buffer(1);
       tab.cut[p] = set->shards[size_t(p)]->col_lo;
     }
     tab.cut[n] = B;
