@@ -68,6 +68,7 @@ EXPORTS = [
     "nidreg_version", "nidreg_colorizer_create", "nidreg_colorizer_update", "nidreg_colorizer_device_colors", "nidreg_colorizer_destroy", "nidreg_generate_lidar_image",
     "nidreg_equalize_intensities", "nidreg_num_shards", "nidreg_shard_devices", "nidreg_trim", "nidreg_eval_batch", "nidreg_submit", "nidreg_submit_iso", "nidreg_wait", "nidreg_eval_pipelined",
     "nidreg_estimate_camera_fov", "nidreg_rccl_unique_id", "nidreg_shard_comm_init", "nidreg_shard_attach_rccl", "nidreg_kernel_build",
+    "nidreg_estimate_directions", "nidreg_ransac_sample_pairs", "nidreg_estimate_rotation_ransac",
 ]
 
 _lib = None
@@ -132,6 +133,11 @@ def load():
     lib.nidreg_trim.restype = None
     lib.nidreg_trim.argtypes = []
     lib.nidreg_estimate_camera_fov.argtypes = [ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p]
+    lib.nidreg_estimate_directions.argtypes = [ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_int64, c_double_p]
+    lib.nidreg_ransac_sample_pairs.argtypes = [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]
+    lib.nidreg_estimate_rotation_ransac.argtypes = [ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
+                                                    ctypes.c_uint64, ctypes.POINTER(ctypes.c_int32), c_double_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                                    ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int32)]
     lib.nidreg_rccl_unique_id.argtypes = [ctypes.c_char_p]
     lib.nidreg_shard_comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]
     lib.nidreg_shard_attach_rccl.argtypes = [ctypes.c_void_p, ctypes.c_void_p]

@@ -101,6 +101,8 @@ hipError_t set_handoff_buffer(void* p);  // nid_kernels_f64.hip (experiment)
 #endif
 // the same scalar projection code run on the host (nid_kernels_f64.hip): host arrays, fp64, 0 = ok
 int project_host(int model, const double* intr, const double* dist, const double* p3, long long n, double* uv, double* jac);
+// vlcal::estimate_direction (estimate_fov.cpp:17-34) over project_host: the bearing of pixel (pu, pv) by NelderMead<2> (nidreg_pose.hip)
+void estimate_direction_host(int model, const double* intr5, const double* dist8, double pu, double pv, double* dir3);
 
 // ViewCulling::cull (nid_cull_kernels.hpp); all pointers are device memory
 hipError_t launch_cull(int model, const double* intr, const double* dist, const double* d_pts, long long stride_d, long long n, const double* T, int W, int H, double min_z,

@@ -33,6 +33,12 @@
  *                            vertex (src/vlcal/preprocess/preprocess.cpp:161-169); VisualLiDARData widens them to
  *                            doubles on the host after loading (src/vlcal/common/visual_lidar_data.cpp:19-26) --
  *                            here the floats are uploaded and widened on the GPU
+ *   nidreg_estimate_directions   vlcal::estimate_direction per keypoint (src/vlcal/common/estimate_fov.cpp:17-34; the loop of
+ *                            src/vlcal/common/estimate_pose.cpp:46-51)
+ *   nidreg_estimate_rotation_ransac  PoseEstimation::estimate_rotation_ransac, the hypothesis loop and the inlier flags
+ *                            (src/vlcal/common/estimate_pose.cpp:53-145)
+ *   nidreg_ransac_sample_pairs   (no reference counterpart) the hypotheses' sampler on the host; replaces the per-thread
+ *                            mt19937 streams of src/vlcal/common/estimate_pose.cpp:90-108
  *   nidreg_destroy           ~NIDCost / ~CostCalculatorNID
  *
  * Conventions
@@ -262,6 +268,31 @@ int nidreg_project(nidreg_handle* h, const double* p3, int64_t n, double* uv, do
  * CostCalculatorNID's max_fov, ViewCulling's min_z and generate_lidar_image take.  Host only (no GPU involved). */
 int nidreg_estimate_camera_fov(int model_id, const double* intrinsics, const double* distortion, int width, int height, double* max_fov);
 int nidreg_project_model(int model_id, const double* intrinsics, const double* distortion, int device_id, int precision, const double* p3, int64_t n, double* uv, double* jac);
+
+/* ---- initial guess: PoseEstimation::estimate_rotation_ransac (src/vlcal/common/estimate_pose.cpp:40-145) ----------------------
+ * nidreg_estimate_directions: vlcal::estimate_direction (estimate_fov.cpp:17-34, NelderMead<2> over the projection) for n pixels,
+ * uv n x 2 -> dirs3 n x 3 (the loop of estimate_pose.cpp:48-51).  Host only, the same code nidreg_estimate_camera_fov runs for its
+ * three pixels; the pixels are spread over at most 16 host threads. */
+int nidreg_estimate_directions(int model_id, const double* intrinsics, const double* distortion, const double* uv, int64_t n, double* dirs3);
+/* The hypotheses nidreg_estimate_rotation_ransac draws when it is given none: pairs[2k], pairs[2k+1] = two DISTINCT indices in
+ * [0, n), a pure function of (seed, k, n) (splitmix64 rounds of a counter; no state, so independent of grid shape and thread
+ * count).  DEVIATION: the reference samples with replacement from mt19937 streams seeded per OpenMP thread
+ * (estimate_pose.cpp:90-108) -- not reproducible across machines, and a pair that names one correspondence twice is a rank-1
+ * problem whose rotation is arbitrary.  Host only.  n >= 2. */
+int nidreg_ransac_sample_pairs(uint64_t seed, int64_t n, int iterations, int32_t* pairs);
+/* estimate_pose.cpp:53-145 on the device: `iterations` hypotheses, each the least-squares rotation between two pairs of UNIT
+ * bearings (find_rotation, :55-83: U diag(1, 1, det U det V) V^T of the SVD of A B^T, here in closed form, fp64), scored by the
+ * number of correspondences with |kp - project(R d_lidar)|^2 < error_thresh^2 (:114-123; strict <, a non-finite projection is an
+ * outlier).  kpts2: n x 2 pixels, dirs_camera3 / dirs_lidar3: n x 3 unit bearings (nidreg_estimate_directions; the normalised
+ * LiDAR points).  sample_pairs: iterations x 2 indices dictating the hypotheses, or NULL = nidreg_ransac_sample_pairs(seed, ...).
+ * A hypothesis whose two bearings coincide (or the same index twice) has no rotation and counts 0 inliers.
+ * The winner is the largest count, ties to the LOWEST iteration (the reference keeps whichever thread entered its critical
+ * section first, :125-130).  R9: its R_camera_lidar, row-major; inlier_flags (n, nullable): :135-142; counts (iterations,
+ * nullable): every hypothesis' count.  best_inliers = counts[best_iteration] = the number of set flags.
+ * NIDREG_ERR_INVALID before any device call: iterations <= 0, n < 2, a NULL input, an unknown model, an index out of range. */
+int nidreg_estimate_rotation_ransac(int model_id, const double* intrinsics, const double* distortion, int device_id, const double* kpts2, const double* dirs_camera3,
+                                    const double* dirs_lidar3, int64_t n, int iterations, double error_thresh, uint64_t seed, const int32_t* sample_pairs, double* R9,
+                                    int32_t* best_iteration, int32_t* best_inliers, uint8_t* inlier_flags, int32_t* counts);
 
 /* ViewCulling::cull (src/vlcal/calib/view_culling.cpp:21-92) on the device: FoV gate against
  * min_z = cos(estimate_camera_fov), in-image test, per-pixel depth buffer (float distance) and the
