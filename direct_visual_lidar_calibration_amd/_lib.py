@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("NIDREG_LIB", os.path.join(CSRC_DIR, "libnidreg.so"))
 
 NIDREG_OK = 0
 NIDREG_FALSE = 1
+NIDREG_ERR_INVALID = -1
 NIDREG_OUT_DOUBLES = 16
 
 MODE_SPLINE, MODE_NEAREST = 0, 1
@@ -69,6 +70,8 @@ EXPORTS = [
     "nidreg_equalize_intensities", "nidreg_num_shards", "nidreg_shard_devices", "nidreg_trim", "nidreg_eval_batch", "nidreg_submit", "nidreg_submit_iso", "nidreg_wait", "nidreg_eval_pipelined",
     "nidreg_estimate_camera_fov", "nidreg_rccl_unique_id", "nidreg_shard_comm_init", "nidreg_shard_attach_rccl", "nidreg_kernel_build",
     "nidreg_estimate_directions", "nidreg_ransac_sample_pairs", "nidreg_estimate_rotation_ransac",
+    "nidreg_integrator_create", "nidreg_integrator_insert", "nidreg_integrator_insert_f32", "nidreg_integrator_size", "nidreg_integrator_get", "nidreg_integrator_info",
+    "nidreg_integrator_destroy",
 ]
 
 _lib = None
@@ -138,6 +141,14 @@ def load():
     lib.nidreg_estimate_rotation_ransac.argtypes = [ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
                                                     ctypes.c_uint64, ctypes.POINTER(ctypes.c_int32), c_double_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                                                     ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int32)]
+    lib.nidreg_integrator_create.argtypes = [ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)]
+    lib.nidreg_integrator_insert.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]
+    lib.nidreg_integrator_insert_f32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64]
+    lib.nidreg_integrator_size.argtypes = [ctypes.c_void_p, c_int64_p]
+    lib.nidreg_integrator_get.argtypes = [ctypes.c_void_p, c_float_p, c_int64_p]
+    lib.nidreg_integrator_info.argtypes = [ctypes.c_void_p, c_int64_p]
+    lib.nidreg_integrator_destroy.restype = None
+    lib.nidreg_integrator_destroy.argtypes = [ctypes.c_void_p]
     lib.nidreg_rccl_unique_id.argtypes = [ctypes.c_char_p]
     lib.nidreg_shard_comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]
     lib.nidreg_shard_attach_rccl.argtypes = [ctypes.c_void_p, ctypes.c_void_p]

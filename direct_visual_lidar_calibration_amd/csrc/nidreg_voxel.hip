@@ -1,0 +1,248 @@
+// nidreg_voxel.hip -- C ABI of the voxel integrator (include/nidreg.h: nidreg_integrator_*): vlcal::StaticPointCloudIntegrator
+// (src/vlcal/preprocess/static_point_cloud_integrator.cpp:25-62) on the device (kernels: nid_voxel_kernels.hpp).  The handle owns
+// the hash table, one frame's upload and the per-point slot scratch of one chunk: device memory is O(occupied voxels + one frame).
+#include "nid_voxel_kernels.hpp"
+#include "nid_launch.hpp"
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+struct nidreg_integrator {
+  int device = 0;
+  double res = 0.0, min_distance = 0.0;
+  int64_t cap = 0;       // slots, a power of two <= kMaxCap
+  int64_t size = 0;      // occupied voxels after the last completed insert
+  int64_t offered = 0;   // points offered by the accepted inserts so far = the next sequence number
+  nidreg::DeviceBuf d_slots;     // VoxSlot[cap]
+  nidreg::DeviceBuf d_counters;  // vox_u64[4]: [0] occupied slots, [1..3] k_vox_check's counts / k_vox_compact's cursor
+  nidreg::DeviceBuf d_frame;     // the frame being inserted (grow-only)
+  size_t frame_bytes = 0;
+  nidreg::DeviceBuf d_slot_of;   // unsigned[min(frame, kChunk)] (grow-only)
+  int64_t slot_of_cap = 0;
+};
+
+namespace nidreg {
+namespace {
+
+constexpr int64_t kInitialCap = int64_t(1) << 16;  // 2 MB
+constexpr int64_t kMaxCap = int64_t(1) << 31;      // slot numbers are 32-bit (64 GB of table)
+constexpr int64_t kChunk = int64_t(1) << 20;       // points per claim / payload launch pair: bounds the slot scratch and how far the table is grown ahead
+
+unsigned vox_grid(int64_t n) { return unsigned(std::max<int64_t>(1, std::min<int64_t>((n + kVoxThreads - 1) / kVoxThreads, kVoxMaxBlocks))); }
+
+int64_t pow2_at_least(int64_t v) {
+  int64_t c = kInitialCap;
+  while (c < v) c <<= 1;
+  return c;
+}
+
+// a table of at least 2 x `need` slots (load factor <= 1/2 once `need` voxels are in): rehash on the device when the current one is smaller
+int vox_reserve(nidreg_integrator* h, int64_t need) {
+  if (2 * need <= h->cap) return NIDREG_OK;
+  if (2 * need > kMaxCap) return fail(NIDREG_ERR_INVALID, "nidreg_integrator_insert: more than 2^30 voxels");
+  const int64_t cap = pow2_at_least(2 * need);
+  DeviceBuf fresh;
+  HIP_TRY(fresh.alloc(size_t(cap) * sizeof(VoxSlot)));
+  HIP_TRY(hipMemsetAsync(fresh.as<void>(), 0, size_t(cap) * sizeof(VoxSlot), nullptr));
+  if (h->size > 0) {
+    hipLaunchKernelGGL(k_vox_rehash, dim3(vox_grid(h->cap)), dim3(kVoxThreads), 0, nullptr, h->d_slots.as<VoxSlot>(), (long long)h->cap, fresh.as<VoxSlot>(), unsigned(cap - 1));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(nullptr));  // the old table is freed below
+  }
+  h->d_slots = std::move(fresh);
+  h->cap = cap;
+  return NIDREG_OK;
+}
+
+int vox_read_size(nidreg_integrator* h, int64_t* size) {
+  vox_u64 v = 0;
+  HIP_TRY(hipMemcpy(&v, h->d_counters.as<vox_u64>(), sizeof(v), hipMemcpyDeviceToHost));  // (synchronises the null stream)
+  *size = int64_t(v);
+  return NIDREG_OK;
+}
+
+// what nidreg_integrator_insert and _insert_f32 share once the frame sits in h->d_frame: the check pass, then claim + payload per chunk
+template <typename Frame>
+int vox_insert(nidreg_integrator* h, const char* who, const Frame& frame, int64_t n) {
+  vox_u64* const d_cnt = h->d_counters.as<vox_u64>();
+  HIP_TRY(hipMemsetAsync(d_cnt + 1, 0, 3 * sizeof(vox_u64), nullptr));
+  hipLaunchKernelGGL((k_vox_check<Frame>), dim3(vox_grid(n)), dim3(kVoxThreads), 0, nullptr, frame, (long long)n, h->res, h->min_distance, d_cnt);
+  HIP_TRY(hipGetLastError());
+  vox_u64 cnt[4];
+  HIP_TRY(hipMemcpy(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost));
+  if (cnt[1] || cnt[2]) {
+    char msg[512];
+    std::snprintf(msg, sizeof(msg),
+                  "%s: %llu point(s) with a non-finite coordinate, %llu point(s) outside the packed-key limit (the voxel index floor(coordinate / voxel_resolution) must lie in "
+                  "[-1048576, 1048576) on every axis: |coordinate| < %g at voxel_resolution %g); nothing was inserted",
+                  who, cnt[1], cnt[2], double(kVoxAxisLimit) * h->res, h->res);
+    return fail(NIDREG_ERR_INVALID, msg);
+  }
+  if (h->slot_of_cap < std::min(n, kChunk)) {
+    HIP_TRY(h->d_slot_of.alloc(size_t(std::min(n, kChunk)) * sizeof(unsigned)));
+    h->slot_of_cap = std::min(n, kChunk);
+  }
+  int64_t size_bound = h->size;  // occupied slots, or an upper bound of them while the chunks run without a read-back
+  for (int64_t i0 = 0; i0 < n; i0 += kChunk) {
+    const int64_t m = std::min(kChunk, n - i0);
+    if (2 * (size_bound + m) > h->cap) {
+      if (const int rc = vox_read_size(h, &h->size)) return rc;
+      size_bound = h->size;
+      if (const int rc = vox_reserve(h, size_bound + m)) return rc;
+    }
+    const vox_u64 seq0 = vox_u64(h->offered + i0);
+    hipLaunchKernelGGL((k_vox_claim<Frame>), dim3(vox_grid(m)), dim3(kVoxThreads), 0, nullptr, frame, (long long)i0, (long long)m, seq0, h->res, h->min_distance, h->d_slots.as<VoxSlot>(),
+                       unsigned(h->cap - 1), h->d_slot_of.as<unsigned>(), d_cnt);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL((k_vox_payload<Frame>), dim3(vox_grid(m)), dim3(kVoxThreads), 0, nullptr, frame, (long long)i0, (long long)m, seq0, h->d_slots.as<VoxSlot>(),
+                       h->d_slot_of.as<unsigned>());
+    HIP_TRY(hipGetLastError());
+    size_bound += m;
+  }
+  if (const int rc = vox_read_size(h, &h->size)) return rc;
+  h->offered += n;
+  return NIDREG_OK;
+}
+
+int vox_frame_room(nidreg_integrator* h, size_t bytes) {
+  if (h->frame_bytes >= bytes) return NIDREG_OK;
+  HIP_TRY(h->d_frame.alloc(bytes));
+  h->frame_bytes = bytes;
+  return NIDREG_OK;
+}
+
+}  // namespace
+}  // namespace nidreg
+
+using namespace nidreg;
+
+extern "C" {
+
+int nidreg_integrator_create(int device_id, double voxel_resolution, double min_distance, nidreg_integrator** out) {
+  if (!out) return fail(NIDREG_ERR_INVALID, "nidreg_integrator_create: null out");
+  *out = nullptr;
+  if (!(voxel_resolution > 0.0) || !std::isfinite(voxel_resolution)) return fail(NIDREG_ERR_INVALID, "nidreg_integrator_create: voxel_resolution must be positive and finite");
+  if (std::isnan(min_distance)) return fail(NIDREG_ERR_INVALID, "nidreg_integrator_create: min_distance is NaN");
+  if (device_id < 0) return fail(NIDREG_ERR_INVALID, "nidreg_integrator_create: device_id out of range");
+  if (const int rc = use_device("nidreg_integrator_create", device_id)) return rc;
+  std::unique_ptr<nidreg_integrator> h(new nidreg_integrator());
+  h->device = device_id;
+  h->res = voxel_resolution;
+  h->min_distance = min_distance;
+  h->cap = kInitialCap;
+  HIP_TRY(h->d_slots.alloc(size_t(h->cap) * sizeof(VoxSlot)));
+  HIP_TRY(h->d_counters.alloc(4 * sizeof(vox_u64)));
+  HIP_TRY(hipMemsetAsync(h->d_slots.as<void>(), 0, size_t(h->cap) * sizeof(VoxSlot), nullptr));
+  HIP_TRY(hipMemsetAsync(h->d_counters.as<void>(), 0, 4 * sizeof(vox_u64), nullptr));
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  *out = h.release();
+  return NIDREG_OK;
+}
+
+int nidreg_integrator_insert(nidreg_integrator* h, const double* points, int64_t point_stride, const double* intensities, int64_t n) {
+  if (!h) return fail(NIDREG_ERR_INVALID, "nidreg_integrator_insert: null integrator");
+  if (n < 0 || (n > 0 && (!points || !intensities))) return fail(NIDREG_ERR_INVALID, "nidreg_integrator_insert: negative n or null points / intensities");
+  if (n == 0) return NIDREG_OK;
+  const int64_t stride = point_stride > 0 ? point_stride : 32;
+  if (stride < 24 || stride % 8 || reinterpret_cast<uintptr_t>(points) % 8 || reinterpret_cast<uintptr_t>(intensities) % 8)
+    return fail(NIDREG_ERR_INVALID, "nidreg_integrator_insert: point_stride must be >= 24 bytes, strides and pointers 8-byte aligned");
+  if (stride > INT64_MAX / n) return fail(NIDREG_ERR_INVALID, "nidreg_integrator_insert: stride x n overflows");
+  HIP_TRY(hipSetDevice(h->device));
+  // device frame: n points of 32 bytes (x y z and an unused fourth double), then n intensities
+  if (const int rc = vox_frame_room(h, size_t(n) * 40)) return rc;
+  unsigned char* const d = h->d_frame.as<unsigned char>();
+  if (stride == 32) {
+    HIP_TRY(hipMemcpy(d, points, size_t(n) * 32, hipMemcpyHostToDevice));
+  } else {
+    HIP_TRY(hipMemcpy2D(d, 32, points, size_t(stride), size_t(std::min<int64_t>(stride, 32)), size_t(n), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipMemcpy(d + size_t(n) * 32, intensities, size_t(n) * 8, hipMemcpyHostToDevice));
+  const VoxFrameF64 frame{reinterpret_cast<const double4*>(d), reinterpret_cast<const double*>(d + size_t(n) * 32)};
+  return vox_insert(h, "nidreg_integrator_insert", frame, n);
+}
+
+int nidreg_integrator_insert_f32(nidreg_integrator* h, const float* points, int64_t point_stride, const float* intensities, int64_t intensity_stride, int64_t n) {
+  if (!h) return fail(NIDREG_ERR_INVALID, "nidreg_integrator_insert_f32: null integrator");
+  if (n < 0 || (n > 0 && (!points || !intensities))) return fail(NIDREG_ERR_INVALID, "nidreg_integrator_insert_f32: negative n or null points / intensities");
+  if (n == 0) return NIDREG_OK;
+  if (point_stride < 12 || intensity_stride < 4) return fail(NIDREG_ERR_INVALID, "nidreg_integrator_insert_f32: point_stride must be >= 12 and intensity_stride >= 4 bytes");
+  if (point_stride % 4 || intensity_stride % 4 || reinterpret_cast<uintptr_t>(points) % 4 || reinterpret_cast<uintptr_t>(intensities) % 4)
+    return fail(NIDREG_ERR_INVALID, "nidreg_integrator_insert_f32: strides and pointers must be 4-byte aligned");
+  if (point_stride > INT64_MAX / n || intensity_stride > INT64_MAX / n) return fail(NIDREG_ERR_INVALID, "nidreg_integrator_insert_f32: stride x n overflows");
+  HIP_TRY(hipSetDevice(h->device));
+  if (const int rc = vox_frame_room(h, size_t(n) * 16)) return rc;
+  // the stored PLY record (x y z intensity, 16 bytes) is uploaded as it lies; any other layout is packed into it on the host first
+  if (point_stride == 16 && intensity_stride == 16 && intensities == points + 3) {
+    HIP_TRY(hipMemcpy(h->d_frame.as<void>(), points, size_t(n) * 16, hipMemcpyHostToDevice));
+  } else {
+    std::vector<float> packed(size_t(n) * 4);
+    const unsigned char* p = reinterpret_cast<const unsigned char*>(points);
+    const unsigned char* q = reinterpret_cast<const unsigned char*>(intensities);
+    for (int64_t i = 0; i < n; i++) {
+      std::memcpy(&packed[size_t(i) * 4], p + i * point_stride, 12);
+      std::memcpy(&packed[size_t(i) * 4 + 3], q + i * intensity_stride, 4);
+    }
+    HIP_TRY(hipMemcpy(h->d_frame.as<void>(), packed.data(), size_t(n) * 16, hipMemcpyHostToDevice));
+  }
+  const VoxFrameF32 frame{h->d_frame.as<const float4>()};
+  return vox_insert(h, "nidreg_integrator_insert_f32", frame, n);
+}
+
+int nidreg_integrator_size(nidreg_integrator* h, int64_t* num_voxels) {
+  if (!h || !num_voxels) return fail(NIDREG_ERR_INVALID, "nidreg_integrator_size: null argument");
+  *num_voxels = h->size;
+  return NIDREG_OK;
+}
+
+int nidreg_integrator_info(nidreg_integrator* h, int64_t* info4) {
+  if (!h || !info4) return fail(NIDREG_ERR_INVALID, "nidreg_integrator_info: null argument");
+  info4[0] = h->size, info4[1] = h->cap, info4[2] = h->offered, info4[3] = int64_t(sizeof(VoxSlot));
+  return NIDREG_OK;
+}
+
+int nidreg_integrator_get(nidreg_integrator* h, float* records16, int64_t* seq) {
+  if (!h) return fail(NIDREG_ERR_INVALID, "nidreg_integrator_get: null integrator");
+  const int64_t m = h->size;
+  if (m == 0) return NIDREG_OK;
+  if (!records16) return fail(NIDREG_ERR_INVALID, "nidreg_integrator_get: null records16");
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t sm = size_t(m);
+  int end_bit = 1;
+  while (end_bit < 64 && (vox_u64(h->offered) >> end_bit) != 0) end_bit++;  // keys are sequence numbers + 1 <= offered
+  DeviceBuf d_keys, d_keys2, d_vals, d_vals2, d_tmp, d_out;
+  HIP_TRY(d_keys.alloc(sm * 8));
+  HIP_TRY(d_keys2.alloc(sm * 8));
+  HIP_TRY(d_vals.alloc(sm * 4));
+  HIP_TRY(d_vals2.alloc(sm * 4));
+  HIP_TRY(d_out.alloc(sm * 24));  // m records, then m sequence numbers
+  vox_u64* const cursor = h->d_counters.as<vox_u64>() + 3;
+  HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(vox_u64), nullptr));
+  hipLaunchKernelGGL(k_vox_compact, dim3(vox_grid(h->cap)), dim3(kVoxThreads), 0, nullptr, h->d_slots.as<const VoxSlot>(), (long long)h->cap, cursor, d_keys.as<vox_u64>(), d_vals.as<unsigned>());
+  HIP_TRY(hipGetLastError());
+  size_t tmp_bytes = 0;
+  HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_keys.as<vox_u64>(), d_keys2.as<vox_u64>(), d_vals.as<unsigned>(), d_vals2.as<unsigned>(), sm, 0, unsigned(end_bit), hipStream_t(nullptr)));
+  HIP_TRY(d_tmp.alloc(std::max<size_t>(tmp_bytes, 1)));
+  HIP_TRY(rocprim::radix_sort_pairs(d_tmp.as<void>(), tmp_bytes, d_keys.as<vox_u64>(), d_keys2.as<vox_u64>(), d_vals.as<unsigned>(), d_vals2.as<unsigned>(), sm, 0, unsigned(end_bit), hipStream_t(nullptr)));
+  float4* const d_rec = d_out.as<float4>();
+  long long* const d_seq = reinterpret_cast<long long*>(d_out.as<unsigned char>() + sm * 16);
+  hipLaunchKernelGGL(k_vox_gather, dim3(vox_grid(m)), dim3(kVoxThreads), 0, nullptr, h->d_slots.as<const VoxSlot>(), d_keys2.as<const vox_u64>(), d_vals2.as<const unsigned>(), (long long)m, d_rec, d_seq);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(records16, d_rec, sm * 16, hipMemcpyDeviceToHost));
+  if (seq) HIP_TRY(hipMemcpy(seq, d_seq, sm * 8, hipMemcpyDeviceToHost));
+  return NIDREG_OK;
+}
+
+void nidreg_integrator_destroy(nidreg_integrator* h) {
+  if (!h) return;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(nullptr);
+  delete h;
+}
+
+}  // extern "C"

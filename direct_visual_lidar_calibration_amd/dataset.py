@@ -8,6 +8,7 @@ here                                    reference
                                         ``<bag>.png`` via ``cv::imread(.., 0)`` + ``<bag>.ply`` via ``glk::load_ply``
 ``read_ply`` / ``write_ply``            ``glk::load_ply`` / ``glk::save_ply_binary`` (Iridescence, not in the tree);
                                         the writer emits what preprocess.cpp:161-169 hands it: float x y z + float intensity
+``read_pcd``                            ``pcl::io::load`` of a PCD map into ``PointXYZI`` (PCL, not in the tree; preprocess_map.cpp:129-131)
 ``read_png_gray`` / ``write_png_gray``  ``cv::imread(path, 0)`` / ``cv::imwrite`` for 8-bit single-channel PNGs
 ``read_calib`` / ``write_calib``        ``calib.json`` (preprocess.cpp:220-232; calibrate.cpp:36-46, 56-65, 128-140)
 ``init_T_lidar_camera(config)``         calibrate.cpp:56-77 (manual guess first, then the automatic one)
@@ -170,6 +171,68 @@ def write_ply(path, points, intensities):
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
         f.write(rec.tobytes())
+
+
+# --------------------------------------------------------------------------------------------- PCD
+def read_pcd(path):
+    """The x y z (and, if present, intensity) fields of a PCD file, ``DATA ascii`` or ``DATA binary`` -- what
+    ``pcl::io::load`` into a ``PointXYZI`` cloud keeps (preprocess_map.cpp:129-131).  Returns what ``read_ply_float32`` returns:
+    ``(xyz (n, 3), intensities (n,))`` float32 (views over one buffer for binary files; zeros where the file has no intensity
+    field).  The four fields must be ``F 4``; other fields are skipped by their SIZE x COUNT.  ``binary_compressed`` and other
+    field types are refused with a ValueError that names what was found."""
+    with open(path, "rb") as f:
+        data = f.read()
+    head = {}
+    pos = 0
+    while "DATA" not in head:
+        nl = data.find(b"\n", pos)
+        if nl < 0:
+            raise ValueError(f"{path}: not a PCD file (no DATA line)")
+        tok = data[pos:nl].decode("ascii", "replace").split()
+        pos = nl + 1
+        if tok and not tok[0].startswith("#"):
+            head[tok[0].upper()] = tok[1:]
+    fields = head.get("FIELDS") or head.get("COLUMNS")
+    if not fields or "SIZE" not in head or "TYPE" not in head:
+        raise ValueError(f"{path}: PCD header without FIELDS / SIZE / TYPE")
+    sizes = [int(v) for v in head["SIZE"]]
+    types = [v.upper() for v in head["TYPE"]]
+    counts = [int(v) for v in head.get("COUNT", ["1"] * len(fields))]
+    if not (len(sizes) == len(types) == len(counts) == len(fields)):
+        raise ValueError(f"{path}: PCD header lists {len(fields)} fields but {len(sizes)} sizes, {len(types)} types, {len(counts)} counts")
+    if "POINTS" in head:
+        n = int(head["POINTS"][0])
+    elif "WIDTH" in head and "HEIGHT" in head:
+        n = int(head["WIDTH"][0]) * int(head["HEIGHT"][0])
+    else:
+        raise ValueError(f"{path}: PCD header without POINTS or WIDTH / HEIGHT")
+    fmt = head["DATA"][0].lower() if head["DATA"] else ""
+    if fmt not in ("ascii", "binary"):
+        raise ValueError(f"{path}: unsupported PCD data format '{fmt}' (ascii and binary are read)")
+    wanted = [k for k in ("x", "y", "z", "intensity") if k in fields]
+    for k in ("x", "y", "z"):
+        if k not in fields:
+            raise ValueError(f"{path}: PCD file has no '{k}' field")
+    for k in wanted:
+        i = fields.index(k)
+        if (types[i], sizes[i], counts[i]) != ("F", 4, 1):
+            raise ValueError(f"{path}: field '{k}' is {types[i]} {sizes[i]} x {counts[i]}; only F 4 x 1 is read")
+    if fmt == "binary":
+        dt = np.dtype({"names": [f"f{i}" for i in range(len(fields))], "formats": [("<f4" if fields[i] in wanted else f"V{sizes[i] * counts[i]}") for i in range(len(fields))]})
+        if pos + n * dt.itemsize > len(data):
+            raise ValueError(f"{path}: truncated PCD point data")
+        rec = np.frombuffer(data, dtype=dt, count=n, offset=pos)
+        cols = {k: rec[f"f{fields.index(k)}"] for k in wanted}
+    else:
+        first = np.concatenate([[0], np.cumsum(counts)])  # first token of every field
+        rows = [ln.split() for ln in data[pos:].decode("ascii", "replace").splitlines() if ln.strip()][:n]
+        if len(rows) < n:
+            raise ValueError(f"{path}: truncated PCD point data")
+        cols = {k: np.array([r[first[fields.index(k)]] for r in rows], dtype=np.float64).astype(np.float32) for k in wanted}
+    xyz = np.empty((n, 3), dtype=np.float32)
+    xyz[:, 0], xyz[:, 1], xyz[:, 2] = cols["x"], cols["y"], cols["z"]
+    inten = np.ascontiguousarray(cols["intensity"]) if "intensity" in cols else np.zeros(n, dtype=np.float32)
+    return xyz, inten
 
 
 # --------------------------------------------------------------------------------------------- PNG

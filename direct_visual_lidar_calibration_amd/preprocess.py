@@ -1,0 +1,185 @@
+"""The building blocks of preprocessing that had no counterpart here yet: the voxel integrator, ``cv::equalizeHist`` and the
+LiDAR field of view.
+
+==================================================  =========================================================
+here                                                reference
+==================================================  =========================================================
+``StaticPointCloudIntegrator(res, min_distance)``   ``vlcal::StaticPointCloudIntegrator`` (static_point_cloud_integrator.cpp:8-62)
+``equalize_hist(image_u8)``                         ``cv::equalizeHist`` (OpenCV, not in the reference tree; preprocess_map.cpp:75)
+``estimate_lidar_fov(points)``                      ``vlcal::estimate_lidar_fov`` (src/vlcal/common/estimate_fov.cpp:53-91)
+==================================================  =========================================================
+
+The integrator is a hash table on the GPU behind ``include/nidreg.h`` (``nidreg_integrator_*``, csrc/nid_voxel_kernels.hpp); there
+is no CPU implementation of it here.  ``equalize_hist`` is host work in the reference too (one pass over one image).
+"""
+import ctypes
+import math
+
+import numpy as np
+
+from . import _lib
+
+
+def _check(rc, what):
+    """NIDREG_ERR_INVALID (a refused frame, a bad argument) is the caller's ValueError; anything else is a runtime failure."""
+    if rc == _lib.NIDREG_ERR_INVALID:
+        raise ValueError(f"{what}: {_lib.last_error()}")
+    return _lib.check(rc, what)
+
+
+class StaticPointCloudIntegrator:
+    """``vlcal::StaticPointCloudIntegrator``: one entry per occupied voxel, the LAST point inserted into it (the reference
+    overwrites, static_point_cloud_integrator.cpp:35).  Defaults as the reference's (:8-12).
+
+    ``get_points`` / ``get_records`` return the voxels in ascending order of the winners' sequence numbers (``last_seq``; the
+    reference's order is ``std::unordered_map`` iteration order).  One narrowing: a voxel index must lie in [-2^20, 2^20) on
+    every axis; a frame with a point beyond that, or with a non-finite coordinate, raises ``ValueError`` and inserts nothing."""
+
+    def __init__(self, voxel_resolution=0.05, min_distance=1.0, device=0):
+        self._lib = _lib.load()
+        self._h = None
+        h = ctypes.c_void_p()
+        _check(self._lib.nidreg_integrator_create(int(device), float(voxel_resolution), float(min_distance), ctypes.byref(h)), "nidreg_integrator_create")
+        self._h = h
+        self.voxel_resolution, self.min_distance, self.device = float(voxel_resolution), float(min_distance), int(device)
+        self.last_seq = None
+
+    def insert_points(self, points, intensities):
+        """``insert_points``: ``points`` (n, 3) or (n, 4) (a fourth column is ignored: ``Frame::points`` is x y z 1),
+        ``intensities`` (n,).  float32 arrays (rows and intensities of any 4-byte stride, e.g. both views of one buffer of PLY
+        records) are uploaded as float32 and widened on the GPU; anything else goes through float64."""
+        points = np.asarray(points)
+        intensities = np.asarray(intensities)
+        if points.ndim != 2 or points.shape[1] not in (3, 4) or intensities.shape != (points.shape[0],):
+            raise ValueError("points must be (n, 3) or (n, 4) and intensities (n,)")
+        n = points.shape[0]
+        f32 = all(a.dtype == np.float32 and a.dtype.isnative for a in (points, intensities))
+        if f32 and (n <= 1 or (points.strides[1] == 4 and points.strides[0] % 4 == 0 and intensities.strides[0] % 4 == 0)):
+            pstride, istride = (points.strides[0], intensities.strides[0]) if n > 1 else (12, 4)
+            rc = self._lib.nidreg_integrator_insert_f32(self._h, points.ctypes.data, pstride, intensities.ctypes.data, istride, n)
+            return _check(rc, "nidreg_integrator_insert_f32")
+        if f32:
+            points, intensities = np.ascontiguousarray(points), np.ascontiguousarray(intensities)
+            rc = self._lib.nidreg_integrator_insert_f32(self._h, points.ctypes.data, points.strides[0], intensities.ctypes.data, 4, n)
+            return _check(rc, "nidreg_integrator_insert_f32")
+        points = np.ascontiguousarray(points, dtype=np.float64)
+        intensities = np.ascontiguousarray(intensities, dtype=np.float64)
+        rc = self._lib.nidreg_integrator_insert(self._h, points.ctypes.data, 8 * points.shape[1], intensities.ctypes.data, n)
+        return _check(rc, "nidreg_integrator_insert")
+
+    def size(self):
+        m = ctypes.c_int64()
+        _check(self._lib.nidreg_integrator_size(self._h, ctypes.byref(m)), "nidreg_integrator_size")
+        return int(m.value)
+
+    def info(self):
+        """``{"voxels", "capacity" (slots of the table), "offered" (points offered so far), "slot_bytes"}``"""
+        v = (ctypes.c_int64 * 4)()
+        _check(self._lib.nidreg_integrator_info(self._h, v), "nidreg_integrator_info")
+        return {"voxels": int(v[0]), "capacity": int(v[1]), "offered": int(v[2]), "slot_bytes": int(v[3])}
+
+    def get_records(self):
+        """The (m, 4) float32 array as stored: x y z intensity per voxel (the PLY record); sets ``last_seq`` (m,) int64."""
+        m = self.size()
+        rec = np.empty((m, 4), dtype=np.float32)
+        seq = np.empty(m, dtype=np.int64)
+        rc = self._lib.nidreg_integrator_get(self._h, rec.ctypes.data_as(_lib.c_float_p), seq.ctypes.data_as(_lib.c_int64_p))
+        _check(rc, "nidreg_integrator_get")
+        self.last_seq = seq
+        return rec
+
+    def get_points(self):
+        """``get_points`` (:49-62): ``(points float32 (m, 3), intensities float32 (m,))``"""
+        rec = self.get_records()
+        return np.ascontiguousarray(rec[:, :3]), np.ascontiguousarray(rec[:, 3])
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.nidreg_integrator_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def equalize_hist(image_u8):
+    """``cv::equalizeHist`` of an 8-bit single-channel image: lookup table from the cumulative histogram, the first non-zero
+    bin as the offset, ``round(scale * (cdf - cdf_min))`` with scale = 255 / (pixels - cdf_min); a constant image is returned
+    unchanged.  The same bytes as ``synth.equalize_hist_u8`` on every input."""
+    img = np.asarray(image_u8)
+    if img.dtype != np.uint8:
+        raise ValueError("equalize_hist: an 8-bit image expected")
+    if img.size == 0:
+        return img.copy()
+    hist = np.bincount(img.reshape(-1), minlength=256).astype(np.float64)
+    i0 = int(np.flatnonzero(hist)[0])
+    total = float(hist.sum())
+    if total == float(hist[i0]):
+        return np.full_like(img, i0)
+    scale = 255.0 / (total - float(hist[i0]))
+    csum = np.cumsum(hist) - hist[: i0 + 1].sum()
+    lut = np.clip(np.rint(csum * scale), 0, 255)
+    lut[: i0 + 1] = 0
+    return lut.astype(np.uint8)[img]
+
+
+def estimate_lidar_fov(points, device=0):
+    """``vlcal::estimate_lidar_fov`` (estimate_fov.cpp:53-91) [rad]: downsample at 0.2 m, round the representatives to float32,
+    drop those closer than 1 m (float norm, :66), take the convex hull (``scipy.spatial.ConvexHull``: qhull, as in PCL) and
+    return ``acos`` of the smallest dot product between the normalised directions of two hull vertices (:80-90, including the
+    reference's ``min_cosine = M_PI`` initial value).
+
+    Two differences from the reference: the representative of a 0.2 m voxel is the last point that fell into it (the voxel
+    integrator above with ``min_distance`` 0), not the centroid ``pcl::VoxelGrid`` computes (PCL is not in the reference tree:
+    its arithmetic is not pinned); and fewer than 4 non-coplanar points raise ``ValueError`` (PCL's hull of such input is
+    whatever qhull's error path leaves)."""
+    from scipy.spatial import ConvexHull, QhullError
+
+    pts = np.asarray(points)
+    if pts.ndim != 2 or pts.shape[1] not in (3, 4):
+        raise ValueError("estimate_lidar_fov: points (n, 3) or (n, 4) expected")
+    if pts.dtype != np.float32:
+        pts = np.ascontiguousarray(pts, dtype=np.float64)
+    integ = StaticPointCloudIntegrator(voxel_resolution=0.2, min_distance=0.0, device=device)
+    try:
+        integ.insert_points(pts, np.zeros(pts.shape[0], dtype=pts.dtype))
+        reps, _ = integ.get_points()
+    finally:
+        integ.close()
+    x, y, z = reps[:, 0], reps[:, 1], reps[:, 2]
+    reps = reps[~(np.sqrt(x * x + y * y + z * z) < np.float32(1.0))]
+    if reps.shape[0] < 4:
+        raise ValueError(f"estimate_lidar_fov: {reps.shape[0]} points further than 1 m after the 0.2 m downsampling; a convex hull needs 4 that are not coplanar")
+    try:
+        hull = ConvexHull(reps.astype(np.float64))
+    except QhullError as e:
+        raise ValueError(f"estimate_lidar_fov: no convex hull (coplanar points?): {str(e).splitlines()[0]}") from None
+    dirs = reps[hull.vertices].astype(np.float64)
+    dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
+    min_cosine = math.pi
+    for s in range(0, dirs.shape[0], 1024):  # all pairs, 1024 rows at a time
+        min_cosine = min(min_cosine, float((dirs[s : s + 1024] @ dirs.T).min()))
+    # (a pair (i, i) has cosine 1 up to rounding and never is the minimum of a hull of four or more vertices)
+    return math.acos(max(-1.0, min_cosine))
+
+
+def lidar_camera(lidar_fov):
+    """preprocess_map.cpp:184-200: the virtual camera the LiDAR image is rendered through, from the LiDAR's field of view [rad].
+    Returns ``(camera_model, intrinsics, (width, height), T_lidar_camera 4x4)``: below 150 degrees a 1024 x 1024 pinhole whose
+    optical axis is the LiDAR's x (AngleAxis(pi/2, Y) AngleAxis(-pi/2, Z), :193) with fx = 1024 / (2 tan(fov / 2)); else a
+    1920 x 960 equirectangular camera (AngleAxis(-pi/2, X), :199).  The rotations are the closed forms (entries 0 and +-1), where
+    Eigen's carry cos(pi/2) = 6e-17."""
+    T = np.eye(4)
+    if lidar_fov < 150.0 * math.pi / 180.0:
+        size = (1024, 1024)
+        ry = np.array([[0.0, 0.0, 1.0], [0.0, 1.0, 0.0], [-1.0, 0.0, 0.0]])
+        rz = np.array([[0.0, 1.0, 0.0], [-1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
+        T[:3, :3] = ry @ rz
+        fx = size[0] / (2.0 * math.tan(lidar_fov / 2.0))
+        return "plumb_bob", [fx, fx, size[0] / 2.0, size[1] / 2.0], size, T
+    size = (1920, 960)
+    T[:3, :3] = np.array([[1.0, 0.0, 0.0], [0.0, 0.0, 1.0], [0.0, -1.0, 0.0]])
+    return "equirectangular", [float(size[0]), float(size[1])], size, T

@@ -39,6 +39,8 @@
  *                            (src/vlcal/common/estimate_pose.cpp:53-145)
  *   nidreg_ransac_sample_pairs   (no reference counterpart) the hypotheses' sampler on the host; replaces the per-thread
  *                            mt19937 streams of src/vlcal/common/estimate_pose.cpp:90-108
+ *   nidreg_integrator_*      vlcal::StaticPointCloudIntegrator, insert_points / get_points
+ *                            (src/vlcal/preprocess/static_point_cloud_integrator.cpp:25-62)
  *   nidreg_destroy           ~NIDCost / ~CostCalculatorNID
  *
  * Conventions
@@ -336,6 +338,45 @@ int nidreg_generate_lidar_image(int model_id, const double* intrinsics, const do
  * NID path then bins.  Device radix sort; stable, i.e. equal intensities keep their index order (the
  * reference's std::sort leaves that order unspecified). */
 int nidreg_equalize_intensities(int device_id, double* intensities, int64_t num_points);
+
+/* ---- voxel integrator: vlcal::StaticPointCloudIntegrator (src/vlcal/preprocess/static_point_cloud_integrator.cpp) -------------
+ * A hash table of voxels on the device (csrc/nid_voxel_kernels.hpp).  The reference's loop (:25-37), per point in order: skip it when
+ * sqrt(x^2 + y^2 + z^2) < min_distance; voxel = floor(x / res), floor(y / res), floor(z / res) in double (a true division and a
+ * floor: -0.1 at res 0.25 is voxel -1); voxelgrid[voxel] = (x, y, z, intensity), OVERWRITING.  So the integrator ends with one
+ * entry per occupied voxel, the LAST point inserted into it over all insert calls.  Here: every point has a sequence number = the
+ * number of points offered by the accepted insert calls before it (int64; skipped points count), and a voxel's entry is the point
+ * with the largest sequence number -- the same entry, whatever order the GPU visits the points in.  Results are bit-reproducible.
+ *   nidreg_integrator_create   the constructor (:16): voxel_resolution > 0 and finite, min_distance not NaN, else
+ *                              NIDREG_ERR_INVALID.  (The reference's defaults, :8-12: 0.05 and 1.0.)  The table's capacity is not
+ *                              an argument: it grows by rehashing on the device.
+ *   nidreg_integrator_insert   insert_points (:25-37).  points: x y z as three consecutive doubles every point_stride bytes (0 = 32,
+ *                              Frame::points; >= 24, a multiple of 8), intensities: n doubles.  n == 0 is a valid insert.
+ *   nidreg_integrator_insert_f32  the same from float32: x y z every point_stride bytes, one float intensity every
+ *                              intensity_stride bytes (the stored 16-byte PLY record is uploaded as it lies, like
+ *                              nidreg_cloud_create_f32); widened exactly on the GPU, so the result has the same bits as
+ *                              nidreg_integrator_insert fed the widened values.
+ *   nidreg_integrator_size     voxelgrid.size()
+ *   nidreg_integrator_get      get_points (:49-62): num_voxels records of 16 bytes, float x y z intensity = `cast<float>()` of the
+ *                              entry (the PLY record: feeds nidreg_cloud_create_f32 and a PLY writer without a repack); seq
+ *                              (nullable): the winners' sequence numbers.  ORDER: ascending sequence number (the reference's is
+ *                              std::unordered_map iteration order, i.e. unspecified): deterministic, identical from run to run.
+ *   nidreg_integrator_info     [0] voxels, [1] slots of the table, [2] points offered so far, [3] bytes per slot
+ * THE ONE NARROWING against the reference: a voxel is identified by its full integer coordinate (never by a hash of it), packed
+ * into 64 bits at 21 bits per axis, so the voxel index must lie in [-2^20, 2^20) = [-1048576, 1048576) on every axis (+-2.1 km at
+ * the reference's 2 mm map resolution; the reference's key is three ints).  A frame that holds a point beyond that, or a point with
+ * a non-finite coordinate (where the reference converts NaN / an overflowing double to int: undefined behaviour), is refused as a
+ * whole with NIDREG_ERR_INVALID BEFORE anything is inserted -- a check pass over the frame runs first --; the integrator is
+ * unchanged, the refused frame's points do not count as offered, and nidreg_last_error() names the limit.
+ * Device memory: the table (32 bytes per slot, at most half full, the winner's record inside its slot), one frame's upload and
+ * 4 bytes per point of a 1M-point chunk; earlier frames are not kept.  Not thread-safe per integrator. */
+typedef struct nidreg_integrator nidreg_integrator;
+int nidreg_integrator_create(int device_id, double voxel_resolution, double min_distance, nidreg_integrator** out);
+int nidreg_integrator_insert(nidreg_integrator* h, const double* points, int64_t point_stride, const double* intensities, int64_t n);
+int nidreg_integrator_insert_f32(nidreg_integrator* h, const float* points, int64_t point_stride, const float* intensities, int64_t intensity_stride, int64_t n);
+int nidreg_integrator_size(nidreg_integrator* h, int64_t* num_voxels);
+int nidreg_integrator_get(nidreg_integrator* h, float* records16 /* num_voxels x {x, y, z, intensity} */, int64_t* seq /* optional, may be NULL */);
+int nidreg_integrator_info(nidreg_integrator* h, int64_t* info4);
+void nidreg_integrator_destroy(nidreg_integrator* h);
 
 /* ---- split-phase evaluation for a pair whose points are sharded across GPUs --------------
  * rank r:  nidreg_shard_hist(h, se3)      zero + accumulate this shard's fixed-point histogram
