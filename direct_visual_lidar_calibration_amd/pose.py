@@ -215,7 +215,8 @@ class PoseEstimation:
 
     def estimate_rotation_ransac(self, proj, kpts_2d, points_3d, device=0, seed=0, pairs=None, log=None):
         """estimate_pose.cpp:40-145.  Returns ``(R_camera_lidar (3, 3), inlier_flags)``; ``self.last_ransac`` keeps the winning
-        iteration, its inlier count and every hypothesis' count."""
+        iteration, its inlier count and every hypothesis' count.  Raises ``ValueError`` when no hypothesis has an inlier (the
+        winner is then iteration 0 and, if that pair is degenerate, its rotation is not finite)."""
         kp = np.asarray(kpts_2d, dtype=np.float64).reshape(-1, 2)
         p = np.asarray(points_3d, dtype=np.float64)[:, :3]
         if log:
@@ -228,6 +229,10 @@ class PoseEstimation:
         R, best_k, best_n, flags, counts = ransac_rotation(proj, kp, dirs_camera, dirs_lidar, self.params.ransac_iterations, self.params.ransac_error_thresh, device=device, seed=seed,
                                                            pairs=pairs)
         self.last_ransac = {"best_iteration": best_k, "best_inliers": best_n, "counts": counts}
+        if best_n <= 0 or not np.isfinite(R).all():
+            # every hypothesis was degenerate (coincident or opposite bearings: its rotation is NaN) or fitted nothing; the
+            # reference would hand its uninitialised best rotation on to the least squares
+            raise ValueError(f"estimate_rotation_ransac: no hypothesis with an inlier among {len(counts)} ({kp.shape[0]} correspondences, threshold {self.params.ransac_error_thresh} px)")
         if log:
             log(f"num_inliers: {best_n} / {kp.shape[0]}")
         return R, flags

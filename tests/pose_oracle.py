@@ -102,6 +102,34 @@ def make_correspondences(camera_name, n, outlier_fraction, seed, num_points=6000
     return scene, np.ascontiguousarray(kpts), np.ascontiguousarray(scene.points[pick]), is_outlier
 
 
+def make_correspondences_without_image(camera_name, n, outlier_fraction, seed, noise_px=0.0):
+    """make_correspondences without synth.make_scene's image (rendering 2048 x 2048 rays takes ten seconds a scene): n pixels
+    uniform in the image, 2.5 px off its border, unprojected and cast onto the walls of synth's room from the camera centre of the
+    true pose, rounded to float32 like a stored cloud.  Keypoints = the oracle's projections of those points under the true pose
+    (+ uniform noise of +-noise_px), a fraction replaced by pixels uniform in the image.  Returns (camera (model, intrinsics,
+    distortion), kpts (n, 2), points (n, 4), is_outlier (n,))."""
+    import torch
+
+    from direct_visual_lidar_calibration_amd import camera_models, se3, synth
+
+    model, intr, dist, W, H = synth.CONFIG_CAMERAS[camera_name]
+    T = se3.to_matrix(synth.true_T_camera_lidar())
+    R, t = T[:3, :3], T[:3, 3]
+    rng = np.random.default_rng(seed)
+    px = rng.uniform([2.5, 2.5], [W - 2.5, H - 2.5], size=(n, 2))
+    bear = camera_models.unproject(model, intr, dist, torch.tensor(px, dtype=torch.float64))
+    X = synth.ray_room(-(R.T @ t), bear @ torch.tensor(R, dtype=torch.float64)).numpy().astype(np.float32).astype(np.float64)
+    kpts = oracle_lib.project(model, list(intr), list(dist), X @ R.T + t)
+    assert np.isfinite(kpts).all() and np.abs(kpts - px).max() < 1e-2  # (float32 points: the pixel is met to ~1e-4 px)
+    if noise_px > 0.0:
+        kpts += rng.uniform(-noise_px, noise_px, size=kpts.shape)
+    is_outlier = np.zeros(n, dtype=bool)
+    is_outlier[rng.choice(n, size=int(round(outlier_fraction * n)), replace=False)] = True
+    kpts[is_outlier] = rng.uniform([0.0, 0.0], [W - 1.0, H - 1.0], size=(int(is_outlier.sum()), 2))
+    points = np.concatenate([X, np.ones((n, 1))], axis=1)
+    return (model, list(intr), list(dist)), np.ascontiguousarray(kpts), points, is_outlier
+
+
 def unit(p):
     p = np.asarray(p, dtype=np.float64)[:, :3]
     return p / np.linalg.norm(p, axis=1, keepdims=True)

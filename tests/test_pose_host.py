@@ -202,6 +202,30 @@ def test_command_line_round_trip_of_calib_json(tmp_path, monkeypatch, capsys):
     assert "use automatically estimated initial guess" in lines
 
 
+def test_a_ransac_without_any_inlier_is_refused_before_the_least_squares(monkeypatch):
+    """Keypoints a million pixels away from every projection: every hypothesis of the stand-in counts 0 inliers and the winner is
+    iteration 0.  estimate_rotation_ransac raises instead of handing that rotation to the least squares; so does a stage that
+    returns a rotation that is not finite (what the device returns when every hypothesis is degenerate)."""
+    monkeypatch.setattr(pose, "ransac_rotation", _numpy_ransac_stage)
+    scene, kpts, pts, _ = pose_oracle.make_correspondences("pinhole_vga", 50, 0.0, seed=6, num_points=5000)
+    proj = nid.create_camera(scene.model, scene.intrinsics, scene.distortion)
+    pe = pose.PoseEstimation(pose.PoseEstimationParams(ransac_iterations=16))
+    R, flags = pe.estimate_rotation_ransac(proj, kpts, pts, seed=1)
+    assert pe.last_ransac["best_inliers"] == int(flags.sum()) > 0 and np.isfinite(R).all()
+    with pytest.raises(ValueError, match="no hypothesis with an inlier"):
+        pe.estimate_rotation_ransac(proj, kpts + 1e6, pts, seed=1)
+    assert pe.last_ransac["best_iteration"] == 0 and pe.last_ransac["best_inliers"] == 0 and not pe.last_ransac["counts"].any()
+    with pytest.raises(ValueError, match="no hypothesis with an inlier"):
+        pe.estimate(proj, kpts + 1e6, pts, seed=1)
+
+    def all_degenerate(proj, kpts_2d, dirs_camera, dirs_lidar, iterations, error_thresh, device=0, seed=0, pairs=None):
+        return np.full((3, 3), np.nan), 0, 0, np.zeros(len(kpts_2d), dtype=bool), np.zeros(iterations, dtype=np.int32)
+
+    monkeypatch.setattr(pose, "ransac_rotation", all_degenerate)
+    with pytest.raises(ValueError, match="no hypothesis with an inlier"):
+        pe.estimate_rotation_ransac(proj, kpts, pts)
+
+
 def test_command_line_errors(tmp_path, monkeypatch):
     monkeypatch.setattr(pose, "ransac_rotation", _numpy_ransac_stage)
     empty = str(tmp_path / "empty")
