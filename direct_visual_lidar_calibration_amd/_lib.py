@@ -70,7 +70,7 @@ EXPORTS = [
     "nidreg_equalize_intensities", "nidreg_num_shards", "nidreg_shard_devices", "nidreg_trim", "nidreg_eval_batch", "nidreg_submit", "nidreg_submit_iso", "nidreg_wait", "nidreg_eval_pipelined",
     "nidreg_estimate_camera_fov", "nidreg_rccl_unique_id", "nidreg_shard_comm_init", "nidreg_shard_attach_rccl", "nidreg_kernel_build",
     "nidreg_estimate_directions", "nidreg_ransac_sample_pairs", "nidreg_estimate_rotation_ransac",
-    "nidreg_integrator_create", "nidreg_integrator_insert", "nidreg_integrator_insert_f32", "nidreg_integrator_size", "nidreg_integrator_get", "nidreg_integrator_info",
+    "nidreg_integrator_create", "nidreg_integrator_insert", "nidreg_integrator_insert_f32", "nidreg_integrator_insert_cloud2", "nidreg_integrator_size", "nidreg_integrator_get", "nidreg_integrator_info",
     "nidreg_integrator_destroy",
 ]
 
@@ -144,6 +144,8 @@ def load():
     lib.nidreg_integrator_create.argtypes = [ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)]
     lib.nidreg_integrator_insert.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]
     lib.nidreg_integrator_insert_f32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64]
+    lib.nidreg_integrator_insert_cloud2.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                    ctypes.c_int32, c_int64_p]
     lib.nidreg_integrator_size.argtypes = [ctypes.c_void_p, c_int64_p]
     lib.nidreg_integrator_get.argtypes = [ctypes.c_void_p, c_float_p, c_int64_p]
     lib.nidreg_integrator_info.argtypes = [ctypes.c_void_p, c_int64_p]

@@ -14,6 +14,8 @@
 //   k_vox_payload  after the maxima have settled (the next launch): the one point whose sequence number the slot holds
 //                  writes its float32 record (x, y, z, intensity; `cast<float>()`, :55-56) into the slot.  Plain stores, no
 //                  float atomics anywhere: the table's contents are a function of the input alone.
+//   k_vox_decode_cloud2  nidreg_integrator_insert_cloud2 only: the raw sensor_msgs/PointCloud2 records, as they lie in the message,
+//                  to the double frame (VoxFrameF64) the three passes above read.
 //   k_vox_rehash   growth: every occupied slot of the old table moves, payload and all, into a table twice (or more) as large.
 //   k_vox_compact / k_vox_gather   nidreg_integrator_get: (sequence number, slot) of the occupied slots, radix-sorted by the
 //                  host side, then the records in that order.
@@ -156,6 +158,68 @@ __global__ __launch_bounds__(kVoxThreads) void k_vox_payload(Frame frame, long l
     double x, y, z, w;
     frame.load(i0 + k, x, y, z, w);
     slots[h].rec = make_float4(float(x), float(y), float(z), float(w));
+  }
+}
+
+// ---- raw sensor_msgs/PointCloud2 records -> VoxFrameF64 (extract_raw_points, ros_cloud_converter.hpp:107-171) -----------------
+// A record is `step` bytes; x y z (all float32 or all float64) and the intensity channel (uint8 / uint16 / uint32 / float32 /
+// float64) sit at arbitrary byte offsets inside it -- 18- and 22-byte records exist, nothing is naturally aligned, so every
+// field is put together from single bytes (little-endian) and never read through a typed pointer.  All conversions to double
+// are exact.  Records of up to kVoxStageStep bytes: one workgroup per tile of kVoxThreads consecutive records, whose byte
+// span is copied into LDS with 16-byte vector loads first -- the span is widened down / up to 16-byte boundaries; the raw
+// buffer is 16-byte aligned and allocated to a multiple of 16 bytes, so the widened span stays inside it -- and the lanes
+// pick their bytes from LDS.  Longer records (a lane would use a small part of what the tile stages) read their bytes from
+// global memory directly.
+enum { kPcUint8 = 2, kPcUint16 = 4, kPcUint32 = 6, kPcFloat32 = 7, kPcFloat64 = 8 };  // sensor_msgs/PointField datatypes
+constexpr int kVoxStageStep = 128;
+constexpr int kVoxStageVecs = kVoxThreads * kVoxStageStep / 16 + 2;  // a tile's span + up to 15 bytes before and after it
+
+struct VoxCloud2 {
+  const unsigned char* raw;  // num_points records of `step` bytes
+  long long n;
+  int step, ox, oy, oz, oi;  // byte offsets of x, y, z, intensity inside a record
+};
+
+template <int Bytes>
+__device__ inline vox_u64 vox_le(const unsigned char* p) {
+  vox_u64 v = 0;
+#pragma unroll
+  for (int k = 0; k < Bytes; k++) v |= vox_u64(p[k]) << (8 * k);
+  return v;
+}
+
+template <int Type>
+__device__ inline double vox_field(const unsigned char* p) {
+  if constexpr (Type == kPcUint8) return double(p[0]);
+  if constexpr (Type == kPcUint16) return double(unsigned(vox_le<2>(p)));
+  if constexpr (Type == kPcUint32) return double(unsigned(vox_le<4>(p)));
+  if constexpr (Type == kPcFloat32) return double(__uint_as_float(unsigned(vox_le<4>(p))));
+  if constexpr (Type == kPcFloat64) return __longlong_as_double((long long)vox_le<8>(p));
+}
+
+template <int XyzType, int IntType, bool Staged>
+__global__ __launch_bounds__(kVoxThreads) void k_vox_decode_cloud2(VoxCloud2 c, double4* pts, double* inten) {
+  __shared__ uint4 stage[Staged ? kVoxStageVecs : 1];
+  const long long tiles = (c.n + kVoxThreads - 1) / kVoxThreads;
+  for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {  // (uniform per workgroup: the barriers below are met by all lanes)
+    const long long i0 = t * kVoxThreads, i = i0 + threadIdx.x;
+    const unsigned char* rec;
+    if constexpr (Staged) {
+      const long long i1 = i0 + kVoxThreads < c.n ? i0 + kVoxThreads : c.n;
+      const long long b0 = i0 * c.step, a0 = b0 & ~15LL;
+      const int vecs = int((i1 * c.step - a0 + 15) >> 4);  // <= kVoxStageVecs: step <= kVoxStageStep
+      const uint4* src = reinterpret_cast<const uint4*>(c.raw + a0);
+      __syncthreads();  // the previous tile has been read
+      for (int v = threadIdx.x; v < vecs; v += kVoxThreads) stage[v] = src[v];
+      __syncthreads();
+      rec = reinterpret_cast<const unsigned char*>(stage) + (b0 - a0) + (long long)threadIdx.x * c.step;
+    } else {
+      rec = c.raw + i * c.step;
+    }
+    if (i < c.n) {
+      pts[i] = make_double4(vox_field<XyzType>(rec + c.ox), vox_field<XyzType>(rec + c.oy), vox_field<XyzType>(rec + c.oz), 0.0);
+      inten[i] = vox_field<IntType>(rec + c.oi);
+    }
   }
 }
 

@@ -1,6 +1,6 @@
 // nidreg_voxel.hip -- C ABI of the voxel integrator (include/nidreg.h: nidreg_integrator_*): vlcal::StaticPointCloudIntegrator
 // (src/vlcal/preprocess/static_point_cloud_integrator.cpp:25-62) on the device (kernels: nid_voxel_kernels.hpp).  The handle owns
-// the hash table, one frame's upload and the per-point slot scratch of one chunk: device memory is O(occupied voxels + one frame).
+// the hash table, one frame's upload (and, for the PointCloud2 route, its decoded form) and the per-point slot scratch of one chunk: device memory is O(occupied voxels + one frame).
 #include "nid_voxel_kernels.hpp"
 #include "nid_launch.hpp"
 
@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstring>
 #include <memory>
+#include <string>
 #include <vector>
 
 struct nidreg_integrator {
@@ -25,6 +26,8 @@ struct nidreg_integrator {
   size_t frame_bytes = 0;
   nidreg::DeviceBuf d_slot_of;   // unsigned[min(frame, kChunk)] (grow-only)
   int64_t slot_of_cap = 0;
+  nidreg::DeviceBuf d_raw;       // nidreg_integrator_insert_cloud2: the message's records as uploaded, a multiple of 16 bytes (grow-only)
+  size_t raw_bytes = 0;
 };
 
 namespace nidreg {
@@ -67,16 +70,28 @@ int vox_read_size(nidreg_integrator* h, int64_t* size) {
   return NIDREG_OK;
 }
 
-// what nidreg_integrator_insert and _insert_f32 share once the frame sits in h->d_frame: the check pass, then claim + payload per chunk
+// what the insert routes share once the frame sits in h->d_frame: the check pass, then claim + payload per chunk.  num_skipped
+// (nidreg_integrator_insert_cloud2): a point with a non-finite coordinate does not refuse the frame; it takes its sequence number,
+// claims nothing (k_vox_claim inserts kVoxOk points only) and is counted there.
 template <typename Frame>
-int vox_insert(nidreg_integrator* h, const char* who, const Frame& frame, int64_t n) {
+int vox_insert(nidreg_integrator* h, const char* who, const Frame& frame, int64_t n, int64_t* num_skipped = nullptr) {
   vox_u64* const d_cnt = h->d_counters.as<vox_u64>();
   HIP_TRY(hipMemsetAsync(d_cnt + 1, 0, 3 * sizeof(vox_u64), nullptr));
   hipLaunchKernelGGL((k_vox_check<Frame>), dim3(vox_grid(n)), dim3(kVoxThreads), 0, nullptr, frame, (long long)n, h->res, h->min_distance, d_cnt);
   HIP_TRY(hipGetLastError());
   vox_u64 cnt[4];
   HIP_TRY(hipMemcpy(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost));
-  if (cnt[1] || cnt[2]) {
+  if (num_skipped) {
+    *num_skipped = int64_t(cnt[1]);
+    if (cnt[2]) {
+      char msg[512];
+      std::snprintf(msg, sizeof(msg),
+                    "%s: %llu point(s) outside the packed-key limit (the voxel index floor(coordinate / voxel_resolution) must lie in [-1048576, 1048576) on every axis: "
+                    "|coordinate| < %g at voxel_resolution %g); nothing was inserted",
+                    who, cnt[2], double(kVoxAxisLimit) * h->res, h->res);
+      return fail(NIDREG_ERR_INVALID, msg);
+    }
+  } else if (cnt[1] || cnt[2]) {
     char msg[512];
     std::snprintf(msg, sizeof(msg),
                   "%s: %llu point(s) with a non-finite coordinate, %llu point(s) outside the packed-key limit (the voxel index floor(coordinate / voxel_resolution) must lie in "
@@ -115,6 +130,29 @@ int vox_frame_room(nidreg_integrator* h, size_t bytes) {
   HIP_TRY(h->d_frame.alloc(bytes));
   h->frame_bytes = bytes;
   return NIDREG_OK;
+}
+
+// sensor_msgs/PointField datatype -> bytes; 0 = not a type the route reads
+int cloud2_type_bytes(int32_t t) { return t == kPcUint8 ? 1 : t == kPcUint16 ? 2 : (t == kPcUint32 || t == kPcFloat32) ? 4 : t == kPcFloat64 ? 8 : 0; }
+
+template <int XyzType, int IntType>
+void cloud2_launch(const VoxCloud2& c, double4* pts, double* inten) {
+  const dim3 grid(vox_grid(c.n)), block(kVoxThreads);
+  if (c.step <= kVoxStageStep)
+    hipLaunchKernelGGL((k_vox_decode_cloud2<XyzType, IntType, true>), grid, block, 0, nullptr, c, pts, inten);
+  else
+    hipLaunchKernelGGL((k_vox_decode_cloud2<XyzType, IntType, false>), grid, block, 0, nullptr, c, pts, inten);
+}
+
+template <int XyzType>
+void cloud2_launch(const VoxCloud2& c, int32_t intensity_datatype, double4* pts, double* inten) {
+  switch (intensity_datatype) {
+    case kPcUint8: return cloud2_launch<XyzType, kPcUint8>(c, pts, inten);
+    case kPcUint16: return cloud2_launch<XyzType, kPcUint16>(c, pts, inten);
+    case kPcUint32: return cloud2_launch<XyzType, kPcUint32>(c, pts, inten);
+    case kPcFloat32: return cloud2_launch<XyzType, kPcFloat32>(c, pts, inten);
+    default: return cloud2_launch<XyzType, kPcFloat64>(c, pts, inten);
+  }
 }
 
 }  // namespace
@@ -192,6 +230,46 @@ int nidreg_integrator_insert_f32(nidreg_integrator* h, const float* points, int6
   }
   const VoxFrameF32 frame{h->d_frame.as<const float4>()};
   return vox_insert(h, "nidreg_integrator_insert_f32", frame, n);
+}
+
+int nidreg_integrator_insert_cloud2(nidreg_integrator* h, const void* data, int64_t num_points, int32_t point_step, int32_t x_offset, int32_t y_offset, int32_t z_offset, int32_t xyz_datatype,
+                                    int32_t intensity_offset, int32_t intensity_datatype, int64_t* num_skipped) {
+  const char* const who = "nidreg_integrator_insert_cloud2";
+  if (num_skipped) *num_skipped = 0;
+  if (!h) return fail(NIDREG_ERR_INVALID, std::string(who) + ": null integrator");
+  if (num_points < 0 || (num_points > 0 && !data)) return fail(NIDREG_ERR_INVALID, std::string(who) + ": negative num_points or null data");
+  if (point_step < 1 || point_step > 65535) return fail(NIDREG_ERR_INVALID, std::string(who) + ": point_step must lie in 1..65535");
+  if (xyz_datatype != kPcFloat32 && xyz_datatype != kPcFloat64)
+    return fail(NIDREG_ERR_INVALID, std::string(who) + ": x, y and z must all be FLOAT32 (7) or all FLOAT64 (8), got datatype " + std::to_string(xyz_datatype));
+  const int xyz_bytes = cloud2_type_bytes(xyz_datatype), int_bytes = cloud2_type_bytes(intensity_datatype);
+  if (!int_bytes) return fail(NIDREG_ERR_INVALID, std::string(who) + ": the intensity must be UINT8, UINT16, UINT32, FLOAT32 or FLOAT64, got datatype " + std::to_string(intensity_datatype));
+  for (const int32_t off : {x_offset, y_offset, z_offset})
+    if (off < 0 || off > point_step - xyz_bytes) return fail(NIDREG_ERR_INVALID, std::string(who) + ": a coordinate field lies outside the point_step bytes of a record");
+  if (intensity_offset < 0 || intensity_offset > point_step - int_bytes) return fail(NIDREG_ERR_INVALID, std::string(who) + ": the intensity field lies outside the point_step bytes of a record");
+  if (num_points == 0) return NIDREG_OK;
+  if (num_points > INT64_MAX / 65535) return fail(NIDREG_ERR_INVALID, std::string(who) + ": num_points x point_step overflows");
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t bytes = size_t(num_points) * size_t(point_step);
+  const size_t room = (bytes + 15) & ~size_t(15);  // the staging loads of k_vox_decode_cloud2 end on a 16-byte boundary
+  if (h->raw_bytes < room) {
+    HIP_TRY(h->d_raw.alloc(room));
+    h->raw_bytes = room;
+  }
+  if (const int rc = vox_frame_room(h, size_t(num_points) * 40)) return rc;
+  HIP_TRY(hipMemcpy(h->d_raw.as<void>(), data, bytes, hipMemcpyHostToDevice));  // the records as they lie in the message
+  unsigned char* const d = h->d_frame.as<unsigned char>();
+  double4* const d_pts = reinterpret_cast<double4*>(d);
+  double* const d_int = reinterpret_cast<double*>(d + size_t(num_points) * 32);
+  const VoxCloud2 c{h->d_raw.as<const unsigned char>(), (long long)num_points, point_step, x_offset, y_offset, z_offset, intensity_offset};
+  if (xyz_datatype == kPcFloat32)
+    cloud2_launch<kPcFloat32>(c, intensity_datatype, d_pts, d_int);
+  else
+    cloud2_launch<kPcFloat64>(c, intensity_datatype, d_pts, d_int);
+  HIP_TRY(hipGetLastError());
+  int64_t skipped = 0;
+  const int rc = vox_insert(h, who, VoxFrameF64{d_pts, d_int}, num_points, &skipped);
+  if (num_skipped) *num_skipped = skipped;
+  return rc;
 }
 
 int nidreg_integrator_size(nidreg_integrator* h, int64_t* num_voxels) {

@@ -237,6 +237,7 @@ def read_pcd(path):
 
 # --------------------------------------------------------------------------------------------- PNG
 _PNG_SIG = b"\x89PNG\r\n\x1a\n"
+PNG_SIGNATURE = _PNG_SIG
 _PNG_CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
 
 
@@ -286,6 +287,11 @@ def read_png(path):
     Returns ``(array (H, W) or (H, W, C), bit_depth)`` with the file's own channel order (RGB)."""
     with open(path, "rb") as f:
         data = f.read()
+    return decode_png(data, path)
+
+
+def decode_png(data, path="PNG data"):
+    """``read_png`` of the file's bytes (a ``sensor_msgs/CompressedImage`` payload); ``path`` names them in error messages"""
     if data[:8] != _PNG_SIG:
         raise ValueError(f"{path}: not a PNG file")
     pos = 8
@@ -347,7 +353,15 @@ def read_png_gray(path):
     """``cv::imread(path, 0)``: an 8-bit single-channel image.  16-bit samples keep their high byte;
     colour images are converted with OpenCV's fixed-point BGR2GRAY weights (R 4899, G 9617, B 1868, >> 14).
     Preprocessed directories only contain 8-bit gray PNGs, for which this is the identity."""
-    img, depth = read_png(path)
+    return _png_to_gray(*read_png(path))
+
+
+def decode_png_gray(data, path="PNG data"):
+    """``cv::imdecode(data, 0)``: ``read_png_gray`` of the file's bytes"""
+    return _png_to_gray(*decode_png(data, path))
+
+
+def _png_to_gray(img, depth):
     if depth == 16:
         img = (img >> 8).astype(np.uint8)
     if img.ndim == 3:

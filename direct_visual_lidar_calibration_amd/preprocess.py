@@ -6,7 +6,12 @@ here                                                reference
 ==================================================  =========================================================
 ``StaticPointCloudIntegrator(res, min_distance)``   ``vlcal::StaticPointCloudIntegrator`` (static_point_cloud_integrator.cpp:8-62)
 ``equalize_hist(image_u8)``                         ``cv::equalizeHist`` (OpenCV, not in the reference tree; preprocess_map.cpp:75)
+``StaticPointCloudIntegrator.insert_cloud2(msg, ch)``  ``extract_raw_points`` (ros_cloud_converter.hpp:62-175) + the finite filter
+                                                    (preprocess.cpp:457) + ``insert_points``, on the message's raw bytes
 ``estimate_lidar_fov(points)``                      ``vlcal::estimate_lidar_fov`` (src/vlcal/common/estimate_fov.cpp:53-91)
+``TimeKeeper().process(stamp, first, last, min)``   ``vlcal::TimeKeeper::process`` (src/vlcal/common/time_keeper.cpp:44-160)
+``equalized_cloud`` / ``save_preprocessed``         what ``preprocess`` and ``preprocess_map`` share after the voxel filter
+                                                    (preprocess.cpp:464-473 and :160-232; preprocess_map.cpp:158-215)
 ==================================================  =========================================================
 
 The integrator is a hash table on the GPU behind ``include/nidreg.h`` (``nidreg_integrator_*``, csrc/nid_voxel_kernels.hpp); there
@@ -14,6 +19,7 @@ is no CPU implementation of it here.  ``equalize_hist`` is host work in the refe
 """
 import ctypes
 import math
+import sys
 
 import numpy as np
 
@@ -66,6 +72,43 @@ class StaticPointCloudIntegrator:
         intensities = np.ascontiguousarray(intensities, dtype=np.float64)
         rc = self._lib.nidreg_integrator_insert(self._h, points.ctypes.data, 8 * points.shape[1], intensities.ctypes.data, n)
         return _check(rc, "nidreg_integrator_insert")
+
+    def insert_cloud2(self, msg_or_fields, intensity_channel):
+        """One ``sensor_msgs/PointCloud2`` frame from its raw bytes: ``extract_raw_points`` (ros_cloud_converter.hpp:62-175), the
+        finite filter of preprocess.cpp:457 and ``insert_points``, with the records uploaded as they lie in the message and
+        decoded on the GPU.  ``msg_or_fields``: a decoded message (``rosbag1.decode_pointcloud2``) or a dict with the same
+        names -- ``fields`` (entries with name / offset / datatype, or such tuples), ``point_step``, ``data`` (bytes-like, at
+        least width x height x point_step bytes), ``width`` and ``height`` (or ``num_points``), ``is_bigendian``.  Returns the
+        number of points skipped for a non-finite coordinate; they still take a sequence number.  Missing x / y / z, a missing
+        intensity channel, mixed or unsupported datatypes and big-endian data raise ``ValueError``."""
+        get = msg_or_fields.get if isinstance(msg_or_fields, dict) else lambda k, d=None: getattr(msg_or_fields, k, d)
+        table = {}
+        for f in get("fields"):
+            name, offset, datatype = (f[0], f[1], f[2]) if isinstance(f, (tuple, list)) else (f.name, f.offset, f.datatype)
+            table[name] = (int(offset), int(datatype))  # (a name listed twice keeps its last entry, as in the reference)
+        if get("is_bigendian"):
+            raise ValueError("insert_cloud2: big-endian point data is not read")
+        for k in ("x", "y", "z"):
+            if k not in table:
+                raise ValueError(f"insert_cloud2: the cloud has no '{k}' field (fields: {', '.join(table)})")
+        if intensity_channel not in table:
+            raise ValueError(f"insert_cloud2: the cloud has no '{intensity_channel}' field to take intensities from (fields: {', '.join(table)})")
+        if not (table["x"][1] == table["y"][1] == table["z"][1]):
+            raise ValueError("insert_cloud2: x, y and z have different datatypes")
+        n = get("num_points")
+        n = int(get("width")) * int(get("height")) if n is None else int(n)
+        step = int(get("point_step"))
+        data = get("data")
+        data = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
+        if data.dtype != np.uint8 or data.ndim != 1 or not data.flags.c_contiguous:
+            raise ValueError("insert_cloud2: data must be a contiguous run of bytes")
+        if n < 0 or step < 1 or data.size < n * step:
+            raise ValueError(f"insert_cloud2: {data.size} data bytes for {n} points of {step} bytes")
+        skipped = ctypes.c_int64()
+        rc = self._lib.nidreg_integrator_insert_cloud2(self._h, data.ctypes.data if n else None, n, step, table["x"][0], table["y"][0], table["z"][0], table["x"][1],
+                                                       table[intensity_channel][0], table[intensity_channel][1], ctypes.byref(skipped))
+        _check(rc, "nidreg_integrator_insert_cloud2")
+        return int(skipped.value)
 
     def size(self):
         m = ctypes.c_int64()
@@ -183,3 +226,104 @@ def lidar_camera(lidar_fov):
     size = (1920, 960)
     T[:3, :3] = np.array([[1.0, 0.0, 0.0], [0.0, 0.0, 1.0], [0.0, -1.0, 0.0]])
     return "equirectangular", [float(size[0]), float(size[1])], size, T
+
+
+class TimeKeeper:
+    """``vlcal::TimeKeeper::process`` (time_keeper.cpp:44-160) with the default ``AbsPointTimeParams`` (time_keeper.hpp:13-16:
+    both true), reduced to what decides whether a frame is kept: the frame's stamp after ``replace_points_stamp``, which reads
+    only the first, the last and the smallest per-point time.  The per-point times themselves are used by the dynamic
+    integrator alone and are not rewritten here.  Warnings go to ``log`` once, as the reference's ``first_warning``."""
+
+    def __init__(self, log=None):
+        self.log = log if log is not None else (lambda msg: print(msg, file=sys.stderr))
+        self.first_warning = True
+        self.last_points_stamp = -1.0
+        self.point_time_offset = 0.0
+        self.stamp = None  # the stamp of the last processed frame after replacement
+
+    def process(self, stamp, first=None, last=None, min_time=None):
+        """``stamp`` [s]; ``first`` / ``last`` / ``min_time``: per-point times of the first and last point and their minimum
+        (callable or value; read only on the negative-time path), ``first=None`` when the cloud has no time field.  Returns
+        ``False`` when the frame must be skipped (its stamp rewinds)."""
+        stamp = self._replace_points_stamp(float(stamp), first, last, min_time)
+        self.stamp = stamp
+        diff = stamp - self.last_points_stamp
+        if self.last_points_stamp < 0.0:
+            pass  # first LiDAR frame
+        elif diff < 0.0:
+            self.log("warning: point timestamp rewind detected!!")
+            self.log(f"       : current:{stamp:.6f} last:{self.last_points_stamp:.6f} diff:{diff:.6f}")
+            return False
+        elif diff > 0.5:
+            self.log("warning: large time gap between consecutive LiDAR frames!!")
+            self.log(f"       : current:{stamp:.6f} last:{self.last_points_stamp:.6f} diff:{diff:.6f}")
+        self.last_points_stamp = stamp
+        return True
+
+    def _replace_points_stamp(self, stamp, first, last, min_time):
+        if first is None:  # :67-83: pseudo per-point times; the stamp stays
+            if self.first_warning:
+                self.log("warning: per-point timestamps are not given!!")
+                self.log("       : use pseudo per-point timestamps based on the order of points")
+                self.first_warning = False
+            return stamp
+        first, last = float(first), float(last)
+        if first < 0.0 or last < 0.0:  # :92-103
+            self.log(f"warning: negative per-point timestamp ({first:.6f} or {last:.6f}) found!!")
+            m = float(min_time() if callable(min_time) else min_time)
+            self.log(f"       : min_stamp={m:.6f}")
+            first, last, stamp = first - m, last - m, stamp - m
+        if first < 1.0:  # :106-108: already relative to the first point
+            return stamp
+        if self.first_warning:
+            self.log(f"warning: large point timestamp ({last:.6f} > 1.0) found!!")
+            self.log("       : assume that point times are absolute and convert them to relative")
+            self.log("       : replace_frame_stamp=1 wrt_first_frame_timestamp=1")
+        if first > 1e16:  # :118-128: nanoseconds
+            if self.first_warning:
+                self.log(f"warning: too large point timestamp ({first:.6f} > 1e16) found!!")
+                self.log("       : maybe using a Livox LiDAR that use FLOAT64 nanosec per-point timestamps")
+                self.log("       : convert per-point timestamps from nanosec to sec")
+            first, last = first * 1e-9, last * 1e-9
+        if abs(stamp - first) < 1.0:  # :132-139
+            if self.first_warning:
+                self.log("warning: use first point timestamp as frame timestamp")
+                self.log(f"       : frame={stamp:.6f} point={first:.6f}")
+            self.point_time_offset = 0.0
+            stamp = first
+        else:  # :140-151 (the offset is taken inside the first-warning block only, as in the reference)
+            if self.first_warning:
+                self.log("warning: point timestamp is too apart from frame timestamp!!")
+                self.log("       : use time offset w.r.t. the first frame timestamp")
+                self.log(f"       : frame={stamp:.6f} point={first:.6f} diff={stamp - first:.6f}")
+                self.point_time_offset = stamp - first
+            stamp = first + self.point_time_offset
+        self.first_warning = False
+        return stamp
+
+
+def equalized_cloud(records, device=0):
+    """The integrator's records -> ``(points (m, 4) float64 homogeneous, intensities (m,) float64)`` with the intensities
+    rank-equalised into 256 levels (preprocess.cpp:464-473, preprocess_map.cpp:158-168); the points are float32 values."""
+    from . import render
+
+    points = np.ones((records.shape[0], 4), dtype=np.float64)
+    points[:, :3] = records[:, :3]
+    intensities = render.equalize_intensities(records[:, 3].astype(np.float64), device=device)
+    return points, intensities
+
+
+def save_preprocessed(dst_path, camera, bags, meta, device=0, log=print):
+    """preprocess.cpp:160-232 / preprocess_map.cpp:173-215: the LiDAR's field of view from the FIRST bag's points, the virtual
+    camera it selects, both LiDAR images of every bag through that camera, and the directory (``dataset.write_preprocessed``).
+    ``bags`` = [(bag_name, image_u8, points (m, 4), intensities (m,))].  Returns ``(config, lidar_fov)``."""
+    from . import dataset, nid, render
+
+    lidar_fov = estimate_lidar_fov(bags[0][2], device=device)
+    log(f"LiDAR FoV: {lidar_fov * 180.0 / math.pi:g}[deg]")
+    model, lidar_intrinsics, size, T_lidar_camera = lidar_camera(lidar_fov)
+    lidar_proj = nid.create_camera(model, lidar_intrinsics, [])
+    T_camera_lidar = np.linalg.inv(T_lidar_camera)
+    lidar_images = {name: render.generate_lidar_image(lidar_proj, size, T_camera_lidar, points, intensities, device=device) for name, _, points, intensities in bags}
+    config = dataset.write_preprocessed(dst_path, camera, bags, meta=meta, lidar_images=lidar_images)
+    return config, lidar_fov

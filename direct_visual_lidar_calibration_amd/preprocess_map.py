@@ -23,12 +23,11 @@ order: equalise the image (``cv::equalizeHist``), voxel-filter the map, rank-equ
 * ``--visualize`` is not offered; ``--device`` is an extension.
 """
 import argparse
-import math
 import sys
 
 import numpy as np
 
-from . import dataset, nid, preprocess, render
+from . import dataset, preprocess
 
 BAG_NAME = "000000"
 _REQUIRED = ("map_path", "image_path", "dst_path", "camera_model", "camera_intrinsics", "camera_distortion_coeffs")
@@ -78,10 +77,7 @@ def load_lidar_points(path, voxel_resolution, device=0, log=print):
     finally:
         integ.close()
     log(f"map_points={xyz.shape[0]} filtered={rec.shape[0]}")
-    points = np.ones((rec.shape[0], 4), dtype=np.float64)
-    points[:, :3] = rec[:, :3]
-    intensities = render.equalize_intensities(rec[:, 3].astype(np.float64), device=device)  # :158-168
-    return points, intensities
+    return preprocess.equalized_cloud(rec, device=device)  # :158-168
 
 
 def run(args, log=print):
@@ -97,14 +93,8 @@ def run(args, log=print):
     points, intensities = load_lidar_points(args.map_path, args.voxel_resolution, device=args.device, log=log)
 
     # save_lidar_data (:173-215)
-    lidar_fov = preprocess.estimate_lidar_fov(points, device=args.device)
-    log(f"LiDAR FoV: {lidar_fov * 180.0 / math.pi:g}[deg]")
-    model, lidar_intrinsics, size, T_lidar_camera = preprocess.lidar_camera(lidar_fov)
-    lidar_proj = nid.create_camera(model, lidar_intrinsics, [])
-    lidar_images = render.generate_lidar_image(lidar_proj, size, np.linalg.inv(T_lidar_camera), points, intensities, device=args.device)
     meta = {"data_path": args.map_path, "camera_info_topic": "N/A", "image_topic": "N/A", "points_topic": "N/A", "intensity_channel": "N/A"}  # :97-106
-    config = dataset.write_preprocessed(args.dst_path, (args.camera_model, intrinsics, distortion), [(BAG_NAME, image, points, intensities)], meta=meta,
-                                        lidar_images={BAG_NAME: lidar_images})
+    config, lidar_fov = preprocess.save_preprocessed(args.dst_path, (args.camera_model, intrinsics, distortion), [(BAG_NAME, image, points, intensities)], meta, device=args.device, log=log)
     return config, points, intensities, lidar_fov
 
 

@@ -355,6 +355,21 @@ int nidreg_equalize_intensities(int device_id, double* intensities, int64_t num_
  *                              intensity_stride bytes (the stored 16-byte PLY record is uploaded as it lies, like
  *                              nidreg_cloud_create_f32); widened exactly on the GPU, so the result has the same bits as
  *                              nidreg_integrator_insert fed the widened values.
+ *   nidreg_integrator_insert_cloud2  the data bytes of a sensor_msgs/PointCloud2 message as they lie in the message: num_points
+ *                              records of point_step bytes (1..65535), uploaded once and decoded on the GPU.  Replaces, per frame,
+ *                              extract_raw_points (include/vlcal/common/ros_cloud_converter.hpp:62-175), the finite filter of
+ *                              src/vlcal/preprocess/preprocess.cpp:457 and insert_points (:25-36).  x, y, z at x/y/z_offset, all of
+ *                              xyz_datatype FLOAT32 (7) or FLOAT64 (8); the intensity channel at intensity_offset, of
+ *                              intensity_datatype UINT8 (2), UINT16 (4), UINT32 (6), FLOAT32 (7) or FLOAT64 (8); all converted to
+ *                              double exactly.  Offsets are arbitrary byte offsets (no alignment is assumed), little-endian.  A point
+ *                              with a non-finite x, y or z is SKIPPED, not refused (the intensity is not tested): it is counted in
+ *                              *num_skipped (nullable) and still takes a sequence number -- point i of the frame has number
+ *                              offered + i and `offered` advances by num_points --, so entries and order equal those of
+ *                              nidreg_integrator_insert fed the decoded, filtered points; only the sequence numbers differ.  A finite
+ *                              point outside the packed-key limit still refuses the whole frame.  NIDREG_ERR_INVALID before any
+ *                              device call: a field outside the record, point_step out of range, another datatype, NULL data with
+ *                              num_points > 0, num_points < 0.  num_points == 0 is a valid insert.  Device memory: the raw frame and
+ *                              40 bytes per point of it.
  *   nidreg_integrator_size     voxelgrid.size()
  *   nidreg_integrator_get      get_points (:49-62): num_voxels records of 16 bytes, float x y z intensity = `cast<float>()` of the
  *                              entry (the PLY record: feeds nidreg_cloud_create_f32 and a PLY writer without a repack); seq
@@ -373,6 +388,8 @@ typedef struct nidreg_integrator nidreg_integrator;
 int nidreg_integrator_create(int device_id, double voxel_resolution, double min_distance, nidreg_integrator** out);
 int nidreg_integrator_insert(nidreg_integrator* h, const double* points, int64_t point_stride, const double* intensities, int64_t n);
 int nidreg_integrator_insert_f32(nidreg_integrator* h, const float* points, int64_t point_stride, const float* intensities, int64_t intensity_stride, int64_t n);
+int nidreg_integrator_insert_cloud2(nidreg_integrator* h, const void* data, int64_t num_points, int32_t point_step, int32_t x_offset, int32_t y_offset, int32_t z_offset, int32_t xyz_datatype,
+                                    int32_t intensity_offset, int32_t intensity_datatype, int64_t* num_skipped);
 int nidreg_integrator_size(nidreg_integrator* h, int64_t* num_voxels);
 int nidreg_integrator_get(nidreg_integrator* h, float* records16 /* num_voxels x {x, y, z, intensity} */, int64_t* seq /* optional, may be NULL */);
 int nidreg_integrator_info(nidreg_integrator* h, int64_t* info4);
