@@ -27,8 +27,9 @@ __global__ __launch_bounds__(256) void k_cull_zbuf(
   const double cz = ((iso.m[8] * x + iso.m[9] * y) + iso.m[10] * z) + iso.m[11] * w;
   const double cw = ((0.0 * x + 0.0 * y) + 0.0 * z) + 1.0 * w;
   int out = -1;
-  const double n4 = sqrt(((cx * cx + cy * cy) + cz * cz) + cw * cw);
-  if (!(cz / n4 < min_z)) {
+  const double s4 = ((cx * cx + cy * cy) + cz * cz) + cw * cw;
+  const double zn = s4 > 0.0 ? cz / sqrt(s4) : cz;  // Eigen normalized(): unchanged when the squared norm is not > 0
+  if (!(zn < min_z)) {
     double u, v;
     project<MODEL, double, double, false>(cam, cx, cy, cz, u, v);
     // .cast<int>() truncates; x86 sends NaN / overflow to INT_MIN (rejected)

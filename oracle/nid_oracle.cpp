@@ -446,9 +446,11 @@ static std::vector<int> view_culling_ref(
 
   for (int64_t i = 0; i < num_points; i++) {
     const double* pc = points_camera.data() + 4 * i;
-    // normalises the 4-vector (x, y, z, 1) -- view_culling.cpp:45
-    const double n4 = std::sqrt(pc[0] * pc[0] + pc[1] * pc[1] + pc[2] * pc[2] + pc[3] * pc[3]);
-    if (pc[2] / n4 < min_z) continue;
+    // normalises the 4-vector (x, y, z, 1) -- view_culling.cpp:45.  Eigen's normalized() returns the vector unchanged when its
+    // squared norm is not > 0 (the point (0, 0, 0, 0), squares that underflow, NaN): then z itself meets the gate
+    const double s4 = pc[0] * pc[0] + pc[1] * pc[1] + pc[2] * pc[2] + pc[3] * pc[3];
+    const double zn = s4 > 0.0 ? pc[2] / std::sqrt(s4) : pc[2];
+    if (zn < min_z) continue;
 
     const V2<double> uv = proj->project(V3<double>{pc[0], pc[1], pc[2]});
     const int px = cast_int(uv.x), py = cast_int(uv.y);
@@ -715,12 +717,15 @@ int oracle_estimate_camera_fov(const char* model, const double* intr, int n_intr
 }
 
 // ViewCulling::cull.  indices_out must hold num_points ints; returns the number kept (or -1).
+// min_z_override (here and in the two entry points below): null derives the gate from the image size as the reference's
+// constructors do; non-null dictates it, so that a test can take the gate out of the way of an image-edge case or put it
+// exactly onto a point.
 int64_t oracle_view_culling(
   const char* model, const double* intr, int n_intr, const double* dist, int n_dist, int width, int height, int enable_depth_buffer_culling, const double* points,
-  int64_t num_points, const double* T, int* indices_out) {
+  int64_t num_points, const double* T, int* indices_out, const double* min_z_override) {
   auto cam = oracle::make_camera(model, intr, n_intr, dist, n_dist);
   if (!cam) return -1;
-  const double min_z = std::cos(oracle::estimate_camera_fov_ref(cam.get(), width, height));
+  const double min_z = min_z_override ? *min_z_override : std::cos(oracle::estimate_camera_fov_ref(cam.get(), width, height));
   const std::vector<int> idx = oracle::view_culling_ref(cam.get(), width, height, min_z, enable_depth_buffer_culling != 0, points, num_points, T);
   std::copy(idx.begin(), idx.end(), indices_out);
   return static_cast<int64_t>(idx.size());
@@ -729,10 +734,10 @@ int64_t oracle_view_culling(
 // PointsColorUpdater::update; min_nz as the constructor computes it: cos(estimate_camera_fov + 0.5 deg)
 int oracle_points_color_update(
   const char* model, const double* intr, int n_intr, const double* dist, int n_dist, const uint8_t* image, int rows, int cols, const double* points, int64_t num_points,
-  const float* intensity_colors, const double* T, double blend_weight, float* colors_out, double* min_nz_out) {
+  const float* intensity_colors, const double* T, double blend_weight, float* colors_out, double* min_nz_out, const double* min_nz_override) {
   auto cam = oracle::make_camera(model, intr, n_intr, dist, n_dist);
   if (!cam) return -1;
-  const double min_nz = std::cos(oracle::estimate_camera_fov_ref(cam.get(), cols, rows) + 0.5 * M_PI / 180.0);
+  const double min_nz = min_nz_override ? *min_nz_override : std::cos(oracle::estimate_camera_fov_ref(cam.get(), cols, rows) + 0.5 * M_PI / 180.0);
   if (min_nz_out) *min_nz_out = min_nz;
   oracle::points_color_update_ref(cam.get(), image, rows, cols, points, num_points, intensity_colors, min_nz, T, blend_weight, colors_out);
   return 0;
@@ -741,10 +746,10 @@ int oracle_points_color_update(
 // generate_lidar_image
 int oracle_generate_lidar_image(
   const char* model, const double* intr, int n_intr, const double* dist, int n_dist, int width, int height, const double* points, const double* intensities, int64_t num_points,
-  const double* T, double* intensity_image, int32_t* index_image) {
+  const double* T, double* intensity_image, int32_t* index_image, const double* min_z_override) {
   auto cam = oracle::make_camera(model, intr, n_intr, dist, n_dist);
   if (!cam) return -1;
-  const double min_z = std::cos(oracle::estimate_camera_fov_ref(cam.get(), width, height));
+  const double min_z = min_z_override ? *min_z_override : std::cos(oracle::estimate_camera_fov_ref(cam.get(), width, height));
   oracle::generate_lidar_image_ref(cam.get(), width, height, min_z, points, intensities, num_points, T, intensity_image, index_image);
   return 0;
 }

@@ -43,6 +43,11 @@ def _dp(a):
     return None if a is None else a.ctypes.data_as(c_double_p)
 
 
+def _opt(value):
+    """optional double by pointer: None -> NULL (the oracle derives the value as the reference does)"""
+    return None if value is None else ctypes.byref(ctypes.c_double(float(value)))
+
+
 def _cam_args(model, intrinsics, distortion):
     intr = np.ascontiguousarray(intrinsics, dtype=np.float64)
     dist = np.ascontiguousarray(distortion if len(distortion) else [0.0], dtype=np.float64)
@@ -157,40 +162,43 @@ def estimate_camera_fov(model, intrinsics, distortion, width, height):
     return out.value
 
 
-def view_culling(model, intrinsics, distortion, width, height, points, T, enable_depth_buffer_culling=True):
+def view_culling(model, intrinsics, distortion, width, height, points, T, enable_depth_buffer_culling=True, min_z=None):
+    """ViewCulling::cull restatement.  min_z: None derives cos(estimate_camera_fov) from the image size as the constructor does."""
     points = np.ascontiguousarray(points, dtype=np.float64)
     T = np.ascontiguousarray(T, dtype=np.float64).reshape(4, 4)
     idx = np.empty(points.shape[0], dtype=np.int32)
     m, ip, ni, dp, nd, keep = _cam_args(model, intrinsics, distortion)
     n = lib().oracle_view_culling(
         m, ip, ni, dp, nd, ctypes.c_int(width), ctypes.c_int(height), ctypes.c_int(1 if enable_depth_buffer_culling else 0), _dp(points), ctypes.c_int64(points.shape[0]),
-        _dp(T), idx.ctypes.data_as(c_int_p),
+        _dp(T), idx.ctypes.data_as(c_int_p), _opt(min_z),
     )
     if n < 0:
         raise ValueError("oracle: bad camera model")
     return idx[:n].copy()
 
 
-def points_color_update(model, intrinsics, distortion, image_u8, points, intensity_colors, T, blend_weight):
-    """PointsColorUpdater::update restatement.  Returns (colors n x 4 float32, min_nz)."""
+def points_color_update(model, intrinsics, distortion, image_u8, points, intensity_colors, T, blend_weight, min_nz=None):
+    """PointsColorUpdater::update restatement.  Returns (colors n x 4 float32, min_nz).  min_nz: None derives
+    cos(estimate_camera_fov + 0.5 deg) as the constructor does."""
     image_u8 = np.ascontiguousarray(image_u8, dtype=np.uint8)
     points = np.ascontiguousarray(points, dtype=np.float64)
     T = np.ascontiguousarray(T, dtype=np.float64).reshape(4, 4)
     ic = np.ascontiguousarray(intensity_colors, dtype=np.float32).reshape(-1, 4)
     out = np.empty((points.shape[0], 4), dtype=np.float32)
-    min_nz = ctypes.c_double(0.0)
+    min_nz_in, min_nz = min_nz, ctypes.c_double(0.0)
     m, ip, ni, dp, nd, keep = _cam_args(model, intrinsics, distortion)
     rc = lib().oracle_points_color_update(
         m, ip, ni, dp, nd, image_u8.ctypes.data_as(c_uint8_p), ctypes.c_int(image_u8.shape[0]), ctypes.c_int(image_u8.shape[1]), _dp(points), ctypes.c_int64(points.shape[0]),
-        ic.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), _dp(T), ctypes.c_double(blend_weight), out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ctypes.byref(min_nz),
+        ic.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), _dp(T), ctypes.c_double(blend_weight), out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ctypes.byref(min_nz), _opt(min_nz_in),
     )
     if rc != 0:
         raise ValueError("oracle: bad camera model")
     return out, min_nz.value
 
 
-def generate_lidar_image(model, intrinsics, distortion, width, height, points, intensities, T):
-    """generate_lidar_image restatement.  Returns (intensity_image H x W float64, index_image H x W int32)."""
+def generate_lidar_image(model, intrinsics, distortion, width, height, points, intensities, T, min_z=None):
+    """generate_lidar_image restatement.  Returns (intensity_image H x W float64, index_image H x W int32).  min_z: None
+    derives cos(estimate_camera_fov) as the function does."""
     points = np.ascontiguousarray(points, dtype=np.float64)
     intensities = np.ascontiguousarray(intensities, dtype=np.float64)
     T = np.ascontiguousarray(T, dtype=np.float64).reshape(4, 4)
@@ -198,7 +206,7 @@ def generate_lidar_image(model, intrinsics, distortion, width, height, points, i
     idx = np.empty((height, width), dtype=np.int32)
     m, ip, ni, dp, nd, keep = _cam_args(model, intrinsics, distortion)
     rc = lib().oracle_generate_lidar_image(
-        m, ip, ni, dp, nd, ctypes.c_int(width), ctypes.c_int(height), _dp(points), _dp(intensities), ctypes.c_int64(points.shape[0]), _dp(T), _dp(iimg), idx.ctypes.data_as(c_int_p),
+        m, ip, ni, dp, nd, ctypes.c_int(width), ctypes.c_int(height), _dp(points), _dp(intensities), ctypes.c_int64(points.shape[0]), _dp(T), _dp(iimg), idx.ctypes.data_as(c_int_p), _opt(min_z),
     )
     if rc != 0:
         raise ValueError("oracle: bad camera model")
