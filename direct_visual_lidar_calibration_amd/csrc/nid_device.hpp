@@ -166,6 +166,32 @@ inline void cam_derive(int model, CamParams<real>& c) {
     c.dist[kAtanD2] = real(2.0 * std::tan(d0 / 2.0));
   }
 }
+inline CamParams<double> make_cam(int model, const double* intr, const double* dist) {
+  CamParams<double> c;
+  for (int i = 0; i < 5; i++) c.intr[i] = intr[i];
+  for (int i = 0; i < 8; i++) c.dist[i] = dist[i];
+  cam_derive<double>(model, c);
+  return c;
+}
+// Host-side dispatch from a run-time value to a template argument, written once: f(std::integral_constant<int, MODEL_X>{}) for the
+// model (`unknown` for an id that is none of the six), f(std::true_type{}) / f(std::false_type{}) for a flag.  f is a generic
+// lambda; its parameter converts to the template argument at compile time: k_project<M, double>, if constexpr (MULTI).
+template <typename R, typename F>
+inline R with_model(int model, R unknown, F&& f) {
+  switch (model) {
+    case MODEL_PLUMB_BOB: return f(std::integral_constant<int, MODEL_PLUMB_BOB>{});
+    case MODEL_FISHEYE: return f(std::integral_constant<int, MODEL_FISHEYE>{});
+    case MODEL_OMNIDIR: return f(std::integral_constant<int, MODEL_OMNIDIR>{});
+    case MODEL_EQUIRECT: return f(std::integral_constant<int, MODEL_EQUIRECT>{});
+    case MODEL_ATAN: return f(std::integral_constant<int, MODEL_ATAN>{});
+    case MODEL_RATIONAL: return f(std::integral_constant<int, MODEL_RATIONAL>{});
+    default: return unknown;
+  }
+}
+template <typename F>
+inline auto with_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
 
 // ------------------------------------------------------------------------------------------
 // a*b + c: one fused multiply-add in the FAST (SPLINE) instantiation when all operands are plain

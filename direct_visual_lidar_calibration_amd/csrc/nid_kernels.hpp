@@ -636,16 +636,7 @@ __global__ __launch_bounds__(WIDE ? kWideThreads : kThreads) void k_spline_hist(
 //             on [0, pi/2] (host):                                                  bu = e1 (A / |c| + C s) + Brel (|u - cx| + |v - cy| + 1);
 //   equirect  (round 5: u, v by two full-precision atan2 with bands A e1 / rho + Bc and C e1 / |c| + Bc2 + D |c| / rho -- 84 us for 10M
 //             points; round 6 decides on the pixel BOUNDARIES instead, without the angles: see below NearestFast)
-struct NearestFast {
-  double er, et;  // 8 eps rmax, 8 eps tmax
-  double A, Bc;
-  double C, D, Bc2;  // (wide-angle models, see above)
-  int on;         // 0: exact tier only (atan / rational_polynomial, or a cone too wide for the model's bound)
-  // equirectangular (round 6): pixel BOUNDARIES instead of pixel coordinates (below)
-  const double* tab_c;  // [kmax + 1][2]: (cos, sin) of theta_k = 2 pi (k / W - 1/2), the longitude of column boundary u = k
-  const double* tab_r;  // [jmax + 1]: t_j = s_j |s_j|, s_j = sin(pi (j / H - 1/2)): the signed squared sine of row boundary v = j
-  int kmax, jmax;       // ceil(W), ceil(H) of the intrinsics
-};
+// (struct NearestFast: nid_multi.hpp, shared with the host, which fills it in)
 
 // Round 6, equirectangular: the decisions WITHOUT the angles.  u = W (1/2 + lon / 2 pi) with lon = atan2(x, z) and v = H (1/2 + lat' / pi)
 // with lat' = asin(y / |c|) are monotone in their angle, so "which column" is "between which two boundary longitudes", and a point lies
@@ -1456,18 +1447,7 @@ __device__ __forceinline__ void grad_reduce_store(const double* acc, double* s_r
 #endif
 }
 
-// what the gradient kernel needs to run the entropy tail itself (k_entropy launched with tail = 0)
-struct GradTail {
-  double* phi_q;             // outputs, written by the pair's first workgroup (nidreg_get_hist, the cost's way to the host)
-  double* hist_image;
-  double* hist_points;
-  EntropyScalars* scal;
-  int from_partials;         // 1: run the tail on the row sums / Hj k_entropy left behind the histogram; 0: read scal / phi_q
-                             // as k_entropy's own tail wrote them; 2: no k_entropy ran at all -- the
-                             // workgroup sums the B x B cells itself (small tables only, grad_entropy_partials)
-  u64* zero_buf;             // from_partials == 2: the histogram buffer of the NEXT evaluation, cleared here (k_entropy's other duty)
-  long long zero_words;
-};
+// (struct GradTail, what the gradient kernel needs to run the entropy tail itself: nid_multi.hpp, shared with the host)
 // Tables of at most this many cells (B <= 32; the reference's default is 16 bins) need no entropy kernel in a cost+Jacobian
 // evaluation: every gradient workgroup reads the whole table -- 1 to 4 cells per thread, about what its G tile costs it
 // anyway -- and gets the same integers k_entropy would have left behind the histogram (sums of ent_fixed terms and of

@@ -5,25 +5,24 @@
 
 namespace nidreg {
 
-template <> hipError_t launch_spline_hist<double>(const PassArgs& a) {
+hipError_t launch_spline_hist(const PassArgs& a) {
   if (a.nchunks == 0) return hipSuccess;
-  return a.rec64 ? launch_spline_hist_rec<double, Rec64>(a) : launch_spline_hist_rec<double, Rec32>(a);
+  return a.rec64 ? spline_hist_rec<Rec64>(a, nullptr) : spline_hist_rec<Rec32>(a, nullptr);
 }
-template <> hipError_t launch_spline_grad<double>(const PassArgs& a) {
+hipError_t launch_spline_grad(const PassArgs& a) {
   if (a.nchunks == 0) return hipSuccess;
-  return a.rec64 ? launch_spline_grad_rec<double, Rec64>(a) : launch_spline_grad_rec<double, Rec32>(a);
+  return a.rec64 ? spline_grad_rec<Rec64>(a, nullptr) : spline_grad_rec<Rec32>(a, nullptr);
 }
-template <> int occupancy_spline_hist<double>(const PassArgs& a) { return a.rec64 ? occupancy_spline_hist_rec<double, Rec64>(a) : occupancy_spline_hist_rec<double, Rec32>(a); }
-template <> int occupancy_spline_grad<double>(const PassArgs& a) { return a.rec64 ? occupancy_spline_grad_rec<double, Rec64>(a) : occupancy_spline_grad_rec<double, Rec32>(a); }
-template <> hipError_t launch_project<double>(int model, const double* intr, const double* dist, const double* p3, long long n, double* uv, double* jac, hipStream_t stream) {
+int occupancy_spline_hist(const PassArgs& a) { return a.rec64 ? occupancy_of(spline_hist_rec<Rec64>, a) : occupancy_of(spline_hist_rec<Rec32>, a); }
+int occupancy_spline_grad(const PassArgs& a) { return a.rec64 ? occupancy_of(spline_grad_rec<Rec64>, a) : occupancy_of(spline_grad_rec<Rec32>, a); }
+hipError_t launch_project(int model, const double* intr, const double* dist, const double* p3, long long n, double* uv, double* jac, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  struct { int model; } a{model};
-  const CamParams<double> cam = make_cam<double>(model, intr, dist);
+  const CamParams<double> cam = make_cam(model, intr, dist);
   const unsigned grid = unsigned((n + 255) / 256);
-#define NID_LAUNCH(M) hipLaunchKernelGGL((k_project<M, double>), dim3(grid), dim3(256), 0, stream, p3, n, cam, uv, jac)
-  NID_MODEL_SWITCH(NID_LAUNCH)
-#undef NID_LAUNCH
-  return hipGetLastError();
+  return with_model(model, hipErrorInvalidValue, [&](auto M) {
+    hipLaunchKernelGGL((k_project<M, double>), dim3(grid), dim3(256), 0, stream, p3, n, cam, uv, jac);
+    return hipGetLastError();
+  });
 }
 
 #ifdef NID_EXP_HANDOFF
@@ -34,27 +33,17 @@ hipError_t set_handoff_buffer(void* p) { return hipMemcpyToSymbol(HIP_SYMBOL(g_u
 // handful of points at a time -- estimate_camera_fov inverts the projection at three pixels with NelderMead<2>, ~240 probes
 // of ONE point (src/vlcal/common/estimate_fov.cpp:17-51), host work in the reference as well
 int project_host(int model, const double* intr, const double* dist, const double* p3, long long n, double* uv, double* jac) {
-  struct { int model; } a{model};
-  const CamParams<double> cam = make_cam<double>(model, intr, dist);
-#define NID_LAUNCH(M)                                                                                      \
-  for (long long i = 0; i < n; i++) {                                                                      \
-    double u, v, du[3], dv[3];                                                                             \
-    project_jac<M, double>(cam, p3[3 * i], p3[3 * i + 1], p3[3 * i + 2], u, v, du, dv);                     \
-    uv[2 * i] = u, uv[2 * i + 1] = v;                                                                      \
-    if (jac)                                                                                               \
-      for (int k = 0; k < 3; k++) jac[6 * i + k] = du[k], jac[6 * i + 3 + k] = dv[k];                      \
-  }
-  switch (a.model) {
-    case MODEL_PLUMB_BOB: NID_LAUNCH(MODEL_PLUMB_BOB) break;
-    case MODEL_FISHEYE: NID_LAUNCH(MODEL_FISHEYE) break;
-    case MODEL_OMNIDIR: NID_LAUNCH(MODEL_OMNIDIR) break;
-    case MODEL_EQUIRECT: NID_LAUNCH(MODEL_EQUIRECT) break;
-    case MODEL_ATAN: NID_LAUNCH(MODEL_ATAN) break;
-    case MODEL_RATIONAL: NID_LAUNCH(MODEL_RATIONAL) break;
-    default: return -1;
-  }
-#undef NID_LAUNCH
-  return 0;
+  const CamParams<double> cam = make_cam(model, intr, dist);
+  return with_model(model, -1, [&](auto M) {
+    for (long long i = 0; i < n; i++) {
+      double u, v, du[3], dv[3];
+      project_jac<M, double>(cam, p3[3 * i], p3[3 * i + 1], p3[3 * i + 2], u, v, du, dv);
+      uv[2 * i] = u, uv[2 * i + 1] = v;
+      if (jac)
+        for (int k = 0; k < 3; k++) jac[6 * i + k] = du[k], jac[6 * i + 3 + k] = dv[k];
+    }
+    return 0;
+  });
 }
 
 }  // namespace nidreg

@@ -1,7 +1,6 @@
-// nid_launch.hpp -- host-visible launch wrappers around the templated kernels.  The double and the
-// float instantiations live in separate translation units because they are compiled with different
-// floating-point contraction rules (nid_kernels_f64.hip: -ffp-contract=off so +,-,*,/,sqrt match the
-// CPU bit for bit; nid_kernels_f32.hip: fused multiply-adds allowed).
+// nid_launch.hpp -- host-visible launch wrappers around the templated kernels.  One precision (double), and every translation
+// unit is built with -ffp-contract=off (csrc/Makefile): the fusions wanted are explicit fma calls, and the NEAREST path's
+// +,-,*,/,sqrt match the CPU bit for bit.
 #pragma once
 #include <string>
 #include <hip/hip_runtime.h>
@@ -19,16 +18,6 @@ namespace nidreg {
 struct Chunk;
 struct EntropyScalars;
 struct ShardTable;
-// k_nearest_hist's fast decision tier (nid_kernels.hpp): error-bound coefficients of this pose and camera, from the host
-struct NearestFastArgs {
-  double er, et, A, Bc;
-  double C, D, Bc2;
-  int on;
-  const double* tab_c;  // equirectangular: boundary tables of the handle (device memory; nid_kernels.hpp NearestFast)
-  const double* tab_r;
-  int kmax, jmax;
-};
-
 struct PassArgs {
   int model;
   int rec64;  // 1: Rec64 records (double xyz), 0: Rec32
@@ -47,7 +36,7 @@ struct PassArgs {
   double magic;     // 2^(frac_bits - 1074): subnormal pre-scale of the x-weights
   double inv_unit;  // 2^(-frac_bits)
   double cos_fov;
-  NearestFastArgs nfast;  // NEAREST: the fast decision tier's band coefficients (on = 0: exact tier only)
+  NearestFast nfast;  // NEAREST: the fast decision tier's band coefficients (on = 0: exact tier only); nid_multi.hpp
   unsigned long long* hist;
   const double* phi_q;
   const EntropyScalars* scal;
@@ -61,27 +50,22 @@ struct PassArgs {
   size_t lds_hist, lds_grad;
   const MultiEntry* multi;  // non-NULL: one grid over several pairs (chunks / nchunks are then the combined table)
   MultiDyn dyn;
-  // the gradient kernel runs the entropy tail itself (k_entropy launched with tail = 0): nid_kernels.hpp GradTail
-  double* gt_phi_q;
-  double* gt_hist_image;
-  double* gt_hist_points;
-  EntropyScalars* gt_scal;
-  int gt_from_partials;
-  void* gt_zero_buf;       // gt_from_partials == 2 (GradTail): the next evaluation's histogram buffer, cleared by the gradient kernel
-  long long gt_zero_words;
+  // the gradient kernel runs the entropy tail itself (k_entropy launched with tail = 0): nid_multi.hpp GradTail.  gt.zero_buf
+  // (gt.from_partials == 2): the next evaluation's histogram buffer, cleared by the gradient kernel
+  GradTail gt;
   int prio;  // progress priority (s_setprio) in the spline passes: set when the evaluation has its device to itself
 };
 
-template <typename real> hipError_t launch_spline_hist(const PassArgs& a);
-template <typename real> hipError_t launch_spline_grad(const PassArgs& a);
-template <typename real> hipError_t launch_nearest_hist(const PassArgs& a);
+hipError_t launch_spline_hist(const PassArgs& a);
+hipError_t launch_spline_grad(const PassArgs& a);
+hipError_t launch_nearest_hist(const PassArgs& a);
 // workgroups of the selected kernel instantiation (model, record type, tiling) that fit on one CU at once
 // (hipOccupancyMaxActiveBlocksPerMultiprocessor; 0 on error): a pass gets exactly one round of co-resident workgroups
-template <typename real> int occupancy_spline_hist(const PassArgs& a);
-template <typename real> int occupancy_spline_grad(const PassArgs& a);
-template <typename real> int occupancy_nearest_hist(const PassArgs& a);
+int occupancy_spline_hist(const PassArgs& a);
+int occupancy_spline_grad(const PassArgs& a);
+int occupancy_nearest_hist(const PassArgs& a);
 // ONE launch per cost+Jacobian evaluation (nid_fused.hpp; small tables, grids of co-resident workgroups): a.chunks / a.nchunks =
-// the fused table, a.hist = this evaluation's histogram buffer, a.gt_zero_buf the next one's
+// the fused table, a.hist = this evaluation's histogram buffer, a.gt.zero_buf the next one's
 struct FusedArgs {
   unsigned long long* barrier;         // arrival counter of the grid barrier (device memory, counts over the handle's lifetime)
   unsigned long long barrier_target;   // arrivals once every workgroup of THIS launch has arrived
@@ -94,7 +78,7 @@ struct FusedArgs {
 size_t fused_lds_bytes_for(const PassArgs& a, int full, int cap);
 hipError_t launch_spline_fused(const PassArgs& a, const FusedArgs& f);
 int occupancy_spline_fused(const PassArgs& a, const FusedArgs& f);  // workgroups of that instantiation per CU (0 on error)
-template <typename real> hipError_t launch_project(int model, const double* intr, const double* dist, const double* p3, long long n, double* uv, double* jac, hipStream_t stream);
+hipError_t launch_project(int model, const double* intr, const double* dist, const double* p3, long long n, double* uv, double* jac, hipStream_t stream);
 
 #ifdef NID_EXP_HANDOFF
 hipError_t set_handoff_buffer(void* p);  // nid_kernels_f64.hip (experiment)

@@ -1,4 +1,5 @@
-// nid_launch_impl.hpp -- bodies of the launch wrappers; included by exactly one TU per `real`.
+// nid_launch_impl.hpp -- bodies of the launch wrappers.  nid_kernels_f64.hip, nid_kernels_f64_exact.hip and nid_kernels_fused.hip
+// each include the whole file and instantiate only the static templates their entry points use.
 #pragma once
 #include <mutex>
 #include <utility>
@@ -9,25 +10,15 @@
 
 namespace nidreg {
 
-template <typename real>
-static CamParams<real> make_cam(int model, const double* intr, const double* dist) {
-  CamParams<real> c;
-  for (int i = 0; i < 5; i++) c.intr[i] = real(intr[i]);
-  for (int i = 0; i < 8; i++) c.dist[i] = real(dist[i]);
-  cam_derive<real>(model, c);  // (constants a model derives from its coefficients: nid_device.hpp)
-  return c;
-}
-template <typename real>
-static PoseParams<real> make_pose(const PassArgs& a) {
-  PoseParams<real> p;
-  for (int i = 0; i < 9; i++) p.R[i] = real(a.R[i]);
-  for (int i = 0; i < 3; i++) p.t[i] = real(a.t[i]);
+static PoseParams<double> make_pose(const PassArgs& a) {
+  PoseParams<double> p;
+  for (int i = 0; i < 9; i++) p.R[i] = a.R[i];
+  for (int i = 0; i < 3; i++) p.t[i] = a.t[i];
   return p;
 }
-template <typename real>
-static IsoParams<real> make_iso(const PassArgs& a) {
-  IsoParams<real> p;
-  for (int i = 0; i < 12; i++) p.m[i] = real(a.iso[i]);
+static IsoParams<double> make_iso(const double* T) {  // rows 0..2 of the 4x4
+  IsoParams<double> p;
+  for (int i = 0; i < 12; i++) p.m[i] = T[i];
   return p;
 }
 
@@ -50,240 +41,80 @@ static hipError_t ensure_lds(K kernel, size_t bytes) {
   return e;
 }
 
-#define NID_MODEL_SWITCH(MACRO)                       \
-  switch (a.model) {                                  \
-    case MODEL_PLUMB_BOB: MACRO(MODEL_PLUMB_BOB); break; \
-    case MODEL_FISHEYE: MACRO(MODEL_FISHEYE); break;  \
-    case MODEL_OMNIDIR: MACRO(MODEL_OMNIDIR); break;  \
-    case MODEL_EQUIRECT: MACRO(MODEL_EQUIRECT); break; \
-    case MODEL_ATAN: MACRO(MODEL_ATAN); break;        \
-    case MODEL_RATIONAL: MACRO(MODEL_RATIONAL); break; \
-    default: return hipErrorInvalidValue;             \
-  }
-
-template <typename real, typename Rec>
-static hipError_t launch_spline_hist_rec(const PassArgs& a) {
-  const PoseParams<real> pose = make_pose<real>(a);
-  const CamParams<real> cam = make_cam<real>(a.model, a.intr, a.dist);
-  // SEG: the table has chunks that run across column-group boundaries (nid_kernels.hpp Segments)
-#define NID_LAUNCH_W(M, WIDE, THREADS, SEG)                                                                                                            \
-  if (a.multi) {                                                                                                                                       \
-    auto k = k_spline_hist<M, Rec, real, WIDE, true, SEG>;                                                                                             \
-    hipError_t e = ensure_lds(k, a.lds_hist);                                                                                                          \
-    if (e != hipSuccess) return e;                                                                                                                     \
-    hipLaunchKernelGGL(k, dim3(a.nchunks), dim3(THREADS), a.lds_hist, a.stream, static_cast<const Rec*>(a.pts), a.chunks, a.gend, a.img, a.pitch, a.W, a.H, pose, \
-                       cam, a.B, a.GW, a.cshift, a.magic, a.hist, a.prio, a.multi, a.dyn);                             \
-  } else {                                                                                                                                             \
-    auto k = k_spline_hist<M, Rec, real, WIDE, false, SEG>;                                                                                            \
-    hipError_t e = ensure_lds(k, a.lds_hist);                                                                                                          \
-    if (e != hipSuccess) return e;                                                                                                                     \
-    hipLaunchKernelGGL(k, dim3(a.nchunks), dim3(THREADS), a.lds_hist, a.stream, static_cast<const Rec*>(a.pts), a.chunks, a.gend, a.img, a.pitch, a.W, a.H, pose, \
-                       cam, a.B, a.GW, a.cshift, a.magic, a.hist, a.prio, a.multi, NoMultiDyn());                      \
-  }
-  if (a.wide) {  // B = 256, GW = 1, 32 copies, 512 threads (see k_spline_hist)
-    if (a.seg) {
-#define NID_LAUNCH(M) NID_LAUNCH_W(M, true, kWideThreads, true)
-      NID_MODEL_SWITCH(NID_LAUNCH)
-#undef NID_LAUNCH
-    } else {
-#define NID_LAUNCH(M) NID_LAUNCH_W(M, true, kWideThreads, false)
-      NID_MODEL_SWITCH(NID_LAUNCH)
-#undef NID_LAUNCH
-    }
-  } else {
-    if (a.seg) {
-#define NID_LAUNCH(M) NID_LAUNCH_W(M, false, kThreads, true)
-      NID_MODEL_SWITCH(NID_LAUNCH)
-#undef NID_LAUNCH
-    } else {
-#define NID_LAUNCH(M) NID_LAUNCH_W(M, false, kThreads, false)
-      NID_MODEL_SWITCH(NID_LAUNCH)
-#undef NID_LAUNCH
-    }
-  }
-#undef NID_LAUNCH_W
+// One workgroup per chunk of a's table; with `occ` nothing is launched: *occ = workgroups of this kernel that fit on one CU at once
+// (`args`, and the pose and camera the passes build for them, are then unused).
+template <typename K, typename... Args>
+static hipError_t launch_chunks(K k, int threads, size_t lds, const PassArgs& a, int* occ, const Args&... args) {
+  const hipError_t e = ensure_lds(k, lds);
+  if (e != hipSuccess) return e;
+  if (occ) return hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, reinterpret_cast<const void*>(k), threads, lds);
+  hipLaunchKernelGGL(k, dim3(a.nchunks), dim3(threads), lds, a.stream, args...);
   return hipGetLastError();
 }
-
-template <typename real, typename Rec>
-static hipError_t launch_spline_grad_rec(const PassArgs& a) {
-  const PoseParams<real> pose = make_pose<real>(a);
-  const CamParams<real> cam = make_cam<real>(a.model, a.intr, a.dist);
-  GradTail gt;
-  gt.phi_q = a.gt_phi_q;
-  gt.hist_image = a.gt_hist_image;
-  gt.hist_points = a.gt_hist_points;
-  gt.scal = a.gt_scal;
-  gt.from_partials = a.gt_from_partials;
-  gt.zero_buf = static_cast<u64*>(a.gt_zero_buf);
-  gt.zero_words = a.gt_zero_words;
-  if (a.seg && a.GW != 1) return hipErrorInvalidValue;  // multi-segment tables are built for the single-column kernels only
-#define NID_LAUNCH_G(M, GW1, SEG)                                                                                                                      \
-  if (a.multi) {                                                                                                                                       \
-    auto k = k_spline_grad<M, Rec, real, GW1, true, SEG>;                                                                                              \
-    hipError_t e = ensure_lds(k, a.lds_grad);                                                                                                          \
-    if (e != hipSuccess) return e;                                                                                                                     \
-    hipLaunchKernelGGL(k, dim3(a.nchunks), dim3(kThreads), a.lds_grad, a.stream, static_cast<const Rec*>(a.pts), a.chunks, a.gend, a.img, a.pitch, a.W, a.H, pose, \
-                       cam, a.B, a.GW, a.cshift, a.inv_unit, a.hist, a.phi_q, a.scal, gt, a.partials, unsigned(a.nslots), a.q[0], a.q[1], a.q[2], a.q[3], a.out, a.out_host, a.tag, \
-                       a.counter, a.prio, a.multi, a.dyn);                                                                                             \
-  } else {                                                                                                                                             \
-    auto k = k_spline_grad<M, Rec, real, GW1, false, SEG>;                                                                                             \
-    hipError_t e = ensure_lds(k, a.lds_grad);                                                                                                          \
-    if (e != hipSuccess) return e;                                                                                                                     \
-    hipLaunchKernelGGL(k, dim3(a.nchunks), dim3(kThreads), a.lds_grad, a.stream, static_cast<const Rec*>(a.pts), a.chunks, a.gend, a.img, a.pitch, a.W, a.H, pose, \
-                       cam, a.B, a.GW, a.cshift, a.inv_unit, a.hist, a.phi_q, a.scal, gt, a.partials, unsigned(a.nslots), a.q[0], a.q[1], a.q[2], a.q[3], a.out, a.out_host, a.tag, \
-                       a.counter, a.prio, a.multi, NoMultiDyn());                                                                                      \
-  }
-  if (a.GW == 1) {
-    if (a.seg) {
-#define NID_LAUNCH(M) NID_LAUNCH_G(M, true, true)
-      NID_MODEL_SWITCH(NID_LAUNCH)
-#undef NID_LAUNCH
-    } else {
-#define NID_LAUNCH(M) NID_LAUNCH_G(M, true, false)
-      NID_MODEL_SWITCH(NID_LAUNCH)
-#undef NID_LAUNCH
-    }
-  } else {
-#define NID_LAUNCH(M) NID_LAUNCH_G(M, false, false)
-    NID_MODEL_SWITCH(NID_LAUNCH)
-#undef NID_LAUNCH
-  }
-#undef NID_LAUNCH_G
-  return hipGetLastError();
+// the last kernel argument: MultiDyn by value in the MULTI instantiations, an empty struct in the others
+template <bool MULTI>
+static typename multi_dyn_of<MULTI>::type dyn_of(const PassArgs& a) {
+  if constexpr (MULTI) return a.dyn;
+  else return NoMultiDyn();
 }
-
-template <typename real, typename Rec>
-static int occupancy_spline_hist_rec(const PassArgs& a) {
+// what an occupancy_* entry point makes of its pass (0 on error)
+template <typename Pass>
+static int occupancy_of(Pass pass, const PassArgs& a) {
   int n = 0;
-#define NID_OCC_W(M, WIDE, THREADS)                                                                                                   \
-  {                                                                                                                                   \
-    auto k = k_spline_hist<M, Rec, real, WIDE, false, false>;                                                                         \
-    if (ensure_lds(k, a.lds_hist) != hipSuccess) return 0;                                                                            \
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(k), THREADS, a.lds_hist) != hipSuccess) n = 0; \
-  }
-  if (a.wide) {
-#define NID_LAUNCH(M) NID_OCC_W(M, true, kWideThreads)
-    switch (a.model) {
-      case MODEL_PLUMB_BOB: NID_LAUNCH(MODEL_PLUMB_BOB); break;
-      case MODEL_FISHEYE: NID_LAUNCH(MODEL_FISHEYE); break;
-      case MODEL_OMNIDIR: NID_LAUNCH(MODEL_OMNIDIR); break;
-      case MODEL_EQUIRECT: NID_LAUNCH(MODEL_EQUIRECT); break;
-      case MODEL_ATAN: NID_LAUNCH(MODEL_ATAN); break;
-      case MODEL_RATIONAL: NID_LAUNCH(MODEL_RATIONAL); break;
-      default: return 0;
-    }
-#undef NID_LAUNCH
-  } else {
-#define NID_LAUNCH(M) NID_OCC_W(M, false, kThreads)
-    switch (a.model) {
-      case MODEL_PLUMB_BOB: NID_LAUNCH(MODEL_PLUMB_BOB); break;
-      case MODEL_FISHEYE: NID_LAUNCH(MODEL_FISHEYE); break;
-      case MODEL_OMNIDIR: NID_LAUNCH(MODEL_OMNIDIR); break;
-      case MODEL_EQUIRECT: NID_LAUNCH(MODEL_EQUIRECT); break;
-      case MODEL_ATAN: NID_LAUNCH(MODEL_ATAN); break;
-      case MODEL_RATIONAL: NID_LAUNCH(MODEL_RATIONAL); break;
-      default: return 0;
-    }
-#undef NID_LAUNCH
-  }
-#undef NID_OCC_W
-  return n;
+  return pass(a, &n) == hipSuccess ? n : 0;
 }
 
-template <typename real, typename Rec>
-static int occupancy_spline_grad_rec(const PassArgs& a) {
-  int n = 0;
-#define NID_OCC_G(M, GW1)                                                                                                             \
-  {                                                                                                                                   \
-    auto k = k_spline_grad<M, Rec, real, GW1, false, false>;                                                                          \
-    if (ensure_lds(k, a.lds_grad) != hipSuccess) return 0;                                                                            \
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(k), kThreads, a.lds_grad) != hipSuccess) n = 0; \
-  }
-  if (a.GW == 1) {
-#define NID_LAUNCH(M) NID_OCC_G(M, true)
-    switch (a.model) {
-      case MODEL_PLUMB_BOB: NID_LAUNCH(MODEL_PLUMB_BOB); break;
-      case MODEL_FISHEYE: NID_LAUNCH(MODEL_FISHEYE); break;
-      case MODEL_OMNIDIR: NID_LAUNCH(MODEL_OMNIDIR); break;
-      case MODEL_EQUIRECT: NID_LAUNCH(MODEL_EQUIRECT); break;
-      case MODEL_ATAN: NID_LAUNCH(MODEL_ATAN); break;
-      case MODEL_RATIONAL: NID_LAUNCH(MODEL_RATIONAL); break;
-      default: return 0;
-    }
-#undef NID_LAUNCH
-  } else {
-#define NID_LAUNCH(M) NID_OCC_G(M, false)
-    switch (a.model) {
-      case MODEL_PLUMB_BOB: NID_LAUNCH(MODEL_PLUMB_BOB); break;
-      case MODEL_FISHEYE: NID_LAUNCH(MODEL_FISHEYE); break;
-      case MODEL_OMNIDIR: NID_LAUNCH(MODEL_OMNIDIR); break;
-      case MODEL_EQUIRECT: NID_LAUNCH(MODEL_EQUIRECT); break;
-      case MODEL_ATAN: NID_LAUNCH(MODEL_ATAN); break;
-      case MODEL_RATIONAL: NID_LAUNCH(MODEL_RATIONAL); break;
-      default: return 0;
-    }
-#undef NID_LAUNCH
-  }
-#undef NID_OCC_G
-  return n;
+// The three passes: each picks its kernel instantiation from `a` and launches it -- or, with `occ`, reports the occupancy of the
+// straight-line single-pair instantiation (MULTI = SEG = false), which is what the planner sizes its tables by.
+template <typename Rec>
+static hipError_t spline_hist_rec(const PassArgs& a, int* occ) {
+  const PoseParams<double> pose = make_pose(a);
+  const CamParams<double> cam = make_cam(a.model, a.intr, a.dist);
+  return with_model(a.model, hipErrorInvalidValue, [&](auto M) {
+    return with_bool(a.wide, [&](auto WIDE) {  // B = 256, GW = 1, 32 copies, 512 threads (see k_spline_hist)
+      return with_bool(!occ && a.seg, [&](auto SEG) {  // the table has chunks that run across column-group boundaries (nid_kernels.hpp Segments)
+        return with_bool(!occ && a.multi, [&](auto MULTI) {
+          return launch_chunks(k_spline_hist<M, Rec, double, WIDE, MULTI, SEG>, WIDE ? kWideThreads : kThreads, a.lds_hist, a, occ, static_cast<const Rec*>(a.pts), a.chunks, a.gend,
+                               a.img, a.pitch, a.W, a.H, pose, cam, a.B, a.GW, a.cshift, a.magic, a.hist, a.prio, a.multi, dyn_of<MULTI>(a));
+        });
+      });
+    });
+  });
 }
 
-// workgroups of the (straight-line, single-pair) NEAREST kernel of this model that fit on one CU at once
-template <typename real, typename Rec>
-static int occupancy_nearest_hist_rec(const PassArgs& a) {
-  int n = 0;
-#define NID_LAUNCH(M)                                                                                                                 \
-  {                                                                                                                                   \
-    auto k = k_nearest_hist<M, Rec, real, false, false>;                                                                              \
-    if (ensure_lds(k, a.lds_hist) != hipSuccess) return 0;                                                                            \
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(k), kThreads, a.lds_hist) != hipSuccess) n = 0; \
-  }
-  switch (a.model) {
-    case MODEL_PLUMB_BOB: NID_LAUNCH(MODEL_PLUMB_BOB); break;
-    case MODEL_FISHEYE: NID_LAUNCH(MODEL_FISHEYE); break;
-    case MODEL_OMNIDIR: NID_LAUNCH(MODEL_OMNIDIR); break;
-    case MODEL_EQUIRECT: NID_LAUNCH(MODEL_EQUIRECT); break;
-    case MODEL_ATAN: NID_LAUNCH(MODEL_ATAN); break;
-    case MODEL_RATIONAL: NID_LAUNCH(MODEL_RATIONAL); break;
-    default: return 0;
-  }
-#undef NID_LAUNCH
-  return n;
+template <typename Rec>
+static hipError_t spline_grad_rec(const PassArgs& a, int* occ) {
+  const PoseParams<double> pose = make_pose(a);
+  const CamParams<double> cam = make_cam(a.model, a.intr, a.dist);
+  return with_model(a.model, hipErrorInvalidValue, [&](auto M) {
+    return with_bool(a.GW == 1, [&](auto GW1) {
+      return with_bool(!occ && a.seg, [&](auto SEG) {
+        return with_bool(!occ && a.multi, [&](auto MULTI) {
+          if constexpr (SEG && !GW1) {
+            return hipErrorInvalidValue;  // multi-segment tables are built for the single-column kernels only
+          } else {
+            return launch_chunks(k_spline_grad<M, Rec, double, GW1, MULTI, SEG>, kThreads, a.lds_grad, a, occ, static_cast<const Rec*>(a.pts), a.chunks, a.gend, a.img, a.pitch, a.W,
+                                 a.H, pose, cam, a.B, a.GW, a.cshift, a.inv_unit, a.hist, a.phi_q, a.scal, a.gt, a.partials, unsigned(a.nslots), a.q[0], a.q[1], a.q[2], a.q[3], a.out,
+                                 a.out_host, a.tag, a.counter, a.prio, a.multi, dyn_of<MULTI>(a));
+          }
+        });
+      });
+    });
+  });
 }
 
-template <typename real, typename Rec>
-static hipError_t launch_nearest_hist_rec(const PassArgs& a) {
-  const IsoParams<real> iso = make_iso<real>(a);
-  const CamParams<real> cam = make_cam<real>(a.model, a.intr, a.dist);
-  NearestFast fast;
-  fast.er = a.nfast.er, fast.et = a.nfast.et, fast.A = a.nfast.A, fast.Bc = a.nfast.Bc, fast.C = a.nfast.C, fast.D = a.nfast.D, fast.Bc2 = a.nfast.Bc2, fast.on = a.nfast.on;
-  fast.tab_c = a.nfast.tab_c, fast.tab_r = a.nfast.tab_r, fast.kmax = a.nfast.kmax, fast.jmax = a.nfast.jmax;
-#define NID_LAUNCH_N(M, SEG)                                                                                                                           \
-  if (a.multi) {                                                                                                                                       \
-    auto k = k_nearest_hist<M, Rec, real, true, SEG>;                                                                                                       \
-    hipError_t e = ensure_lds(k, a.lds_hist);                                                                                                          \
-    if (e != hipSuccess) return e;                                                                                                                     \
-    hipLaunchKernelGGL(k, dim3(a.nchunks), dim3(kThreads), a.lds_hist, a.stream, static_cast<const Rec*>(a.pts), a.chunks, a.gend, a.img, a.pitch, a.W, a.H, iso, cam,  \
-                       a.B, a.GW, a.cshift, real(a.cos_fov), fast, a.hist, a.multi, a.dyn);                                                                   \
-  } else {                                                                                                                                             \
-    auto k = k_nearest_hist<M, Rec, real, false, SEG>;                                                                                                      \
-    hipError_t e = ensure_lds(k, a.lds_hist);                                                                                                          \
-    if (e != hipSuccess) return e;                                                                                                                     \
-    hipLaunchKernelGGL(k, dim3(a.nchunks), dim3(kThreads), a.lds_hist, a.stream, static_cast<const Rec*>(a.pts), a.chunks, a.gend, a.img, a.pitch, a.W, a.H, iso, cam,  \
-                       a.B, a.GW, a.cshift, real(a.cos_fov), fast, a.hist, a.multi, NoMultiDyn());                                                            \
-  }
-  if (a.seg) {
-#define NID_LAUNCH(M) NID_LAUNCH_N(M, true)
-    NID_MODEL_SWITCH(NID_LAUNCH)
-#undef NID_LAUNCH
-  } else {
-#define NID_LAUNCH(M) NID_LAUNCH_N(M, false)
-    NID_MODEL_SWITCH(NID_LAUNCH)
-#undef NID_LAUNCH
-  }
-#undef NID_LAUNCH_N
-  return hipGetLastError();
+template <typename Rec>
+static hipError_t nearest_hist_rec(const PassArgs& a, int* occ) {
+  const IsoParams<double> iso = make_iso(a.iso);
+  const CamParams<double> cam = make_cam(a.model, a.intr, a.dist);
+  return with_model(a.model, hipErrorInvalidValue, [&](auto M) {
+    return with_bool(!occ && a.seg, [&](auto SEG) {
+      return with_bool(!occ && a.multi, [&](auto MULTI) {
+        return launch_chunks(k_nearest_hist<M, Rec, double, MULTI, SEG>, kThreads, a.lds_hist, a, occ, static_cast<const Rec*>(a.pts), a.chunks, a.gend, a.img, a.pitch, a.W, a.H, iso,
+                             cam, a.B, a.GW, a.cshift, a.cos_fov, a.nfast, a.hist, a.multi, dyn_of<MULTI>(a));
+      });
+    });
+  });
 }
 
 }  // namespace nidreg

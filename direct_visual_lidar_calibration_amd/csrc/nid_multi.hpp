@@ -47,6 +47,31 @@ struct MultiDyn {
   int neb;  // entropy workgroups per pair
 };
 
+// Two more kernel-argument structs the host fills in directly (PassArgs, nid_launch.hpp).
+// k_nearest_hist's fast decision tier: error-bound coefficients of this pose and camera (derivations: nid_kernels.hpp, at k_nearest_hist)
+struct NearestFast {
+  double er, et;  // 8 eps rmax, 8 eps tmax
+  double A, Bc;
+  double C, D, Bc2;  // (wide-angle models)
+  int on;         // 0: exact tier only (atan / rational_polynomial, or a cone too wide for the model's bound)
+  // equirectangular (round 6): pixel BOUNDARIES instead of pixel coordinates
+  const double* tab_c;  // [kmax + 1][2]: (cos, sin) of theta_k = 2 pi (k / W - 1/2), the longitude of column boundary u = k
+  const double* tab_r;  // [jmax + 1]: t_j = s_j |s_j|, s_j = sin(pi (j / H - 1/2)): the signed squared sine of row boundary v = j
+  int kmax, jmax;       // ceil(W), ceil(H) of the intrinsics
+};
+// what the gradient kernel needs to run the entropy tail itself (k_entropy launched with tail = 0)
+struct GradTail {
+  double* phi_q;             // outputs, written by the pair's first workgroup (nidreg_get_hist, the cost's way to the host)
+  double* hist_image;
+  double* hist_points;
+  EntropyScalars* scal;
+  int from_partials;         // 1: run the tail on the row sums / Hj k_entropy left behind the histogram; 0: read scal / phi_q
+                             // as k_entropy's own tail wrote them; 2: no k_entropy ran at all -- the
+                             // workgroup sums the B x B cells itself (small tables only, grad_entropy_partials)
+  u64* zero_buf;             // from_partials == 2: the histogram buffer of the NEXT evaluation, cleared here (k_entropy's other duty)
+  long long zero_words;
+};
+
 
 // A pointer READ FROM DEVICE MEMORY (this table) is a generic pointer to the compiler: every access through it becomes a
 // FLAT instruction -- 64-bit per-lane addresses instead of an SGPR base + 32-bit lane offset, and, worse, FLAT loads count

@@ -478,7 +478,7 @@ int nidreg_project(nidreg_handle* h, const double* p3, int64_t n, double* uv, do
     std::memcpy(host, p3, size_t(n) * 3 * sizeof(double));
     double* d_uv = sp.dev + 3 * kSmallProject;
     double* d_j = jac ? sp.dev + 5 * kSmallProject : nullptr;
-    hipError_t e = launch_project<double>(h->model, h->intr, h->dist, sp.dev, n, d_uv, d_j, h->stream);
+    hipError_t e = launch_project(h->model, h->intr, h->dist, sp.dev, n, d_uv, d_j, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return fail(NIDREG_ERR_HIP, std::string("nidreg_project: ") + hipGetErrorString(e));
     std::memcpy(uv, host + 3 * kSmallProject, size_t(n) * 2 * sizeof(double));
@@ -490,7 +490,7 @@ int nidreg_project(nidreg_handle* h, const double* p3, int64_t n, double* uv, do
   HIP_TRY(d_uv.alloc(size_t(n) * 2 * sizeof(double)));
   if (jac) HIP_TRY(d_j.alloc(size_t(n) * 6 * sizeof(double)));
   HIP_TRY(hipMemcpy(d_p.as<void>(), p3, size_t(n) * 3 * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(launch_project<double>(h->model, h->intr, h->dist, d_p.as<double>(), n, d_uv.as<double>(), d_j.as<double>(), h->stream));
+  HIP_TRY(launch_project(h->model, h->intr, h->dist, d_p.as<double>(), n, d_uv.as<double>(), d_j.as<double>(), h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipMemcpy(uv, d_uv.as<void>(), size_t(n) * 2 * sizeof(double), hipMemcpyDeviceToHost));
   if (jac) HIP_TRY(hipMemcpy(jac, d_j.as<void>(), size_t(n) * 6 * sizeof(double), hipMemcpyDeviceToHost));

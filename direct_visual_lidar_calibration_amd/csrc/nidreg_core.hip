@@ -179,10 +179,10 @@ void fill_pass_args(const nidreg_handle* h, PassArgs& a, double* out_host) {
   a.out_host = result_target(h, out_host);
   a.tag = h->seq;
   a.counter = h->d_counters + 1;
-  a.gt_phi_q = h->d_phi_q;
-  a.gt_hist_image = h->d_hist_image;
-  a.gt_hist_points = h->d_hist_points;
-  a.gt_scal = h->d_scal;
+  a.gt.phi_q = h->d_phi_q;
+  a.gt.hist_image = h->d_hist_image;
+  a.gt.hist_points = h->d_hist_points;
+  a.gt.scal = h->d_scal;
   a.stream = h->stream;
   a.lds_hist = h->lds_hist;
   a.lds_grad = h->lds_grad;
@@ -223,7 +223,7 @@ int launch_hist_spline(nidreg_handle* h, const double* se3, bool alone) {
   std::memcpy(a.R, h->last_R, sizeof(a.R));
   std::memcpy(a.t, h->last_t, sizeof(a.t));
   RC_TRY(mark_kernel(h, 1));
-  HIP_TRY(launch_spline_hist<double>(a));
+  HIP_TRY(launch_spline_hist(a));
   return NIDREG_OK;
 }
 
@@ -231,8 +231,8 @@ int launch_hist_spline(nidreg_handle* h, const double* se3, bool alone) {
 // this camera (derivations at the kernel).  plumb_bob and omnidir: only for a FoV cone over which the normalised image
 // coordinates stay bounded (tan(max_fov), resp. sin / (cos + xi)); fisheye and equirectangular: any cone (their bands are
 // per point); atan and rational_polynomial keep the exact tier.  NIDREG_NEAREST_EXACT=1 switches the tier off (A/B runs).
-NearestFastArgs nearest_fast_args(const nidreg_handle* h, const double* T) {
-  NearestFastArgs f;
+NearestFast nearest_fast_args(const nidreg_handle* h, const double* T) {
+  NearestFast f;
   std::memset(&f, 0, sizeof(f));
   static const bool off = [] {
     const char* e = std::getenv("NIDREG_NEAREST_EXACT");
@@ -311,7 +311,7 @@ int launch_hist_nearest(nidreg_handle* h, const double* T) {
   a.nfast = nearest_fast_args(h, T);
   for (int k = 0; k < 12; k++) a.iso[k] = T[k];
   RC_TRY(mark_kernel(h, 1));
-  HIP_TRY(launch_nearest_hist<double>(a));
+  HIP_TRY(launch_nearest_hist(a));
   return NIDREG_OK;
 }
 
@@ -349,16 +349,16 @@ int launch_grad(nidreg_handle* h, bool alone, int from_partials, double* out_hos
   PassArgs a;
   fill_pass_args(h, a, out_host);  // (a.hist = the finished histogram; for a shard: its own columns)
   a.prio = alone ? 1 : 0;
-  a.gt_from_partials = from_partials;
+  a.gt.from_partials = from_partials;
   if (from_partials == 2) {
-    a.gt_zero_buf = h->hist.idle();
-    a.gt_zero_words = h->hist.words();
+    a.gt.zero_buf = h->hist.idle();
+    a.gt.zero_words = h->hist.words();
     h->hist.idle_cleared_on(h->stream);  // zeroed by this evaluation's gradient kernel for the next one
   }
   // same pose as the histogram pass of this evaluation
   std::memcpy(a.R, h->last_R, sizeof(a.R));
   std::memcpy(a.t, h->last_t, sizeof(a.t));
-  HIP_TRY(launch_spline_grad<double>(a));
+  HIP_TRY(launch_spline_grad(a));
   RC_TRY(mark_kernel(h, 4));
   if (h->nchunks == 0) {  // empty cloud: no gradient workgroups ran, finalise (zeros) stand-alone
     HIP_TRY(launch_grad_final(h->stream, h->d_partials, h->last_q, h->d_out, a.out_host, h->seq));
@@ -461,8 +461,8 @@ int eval_launch_fused(nidreg_handle* h, const double* se3) {
   fill_pass_args(h, a);  // (after begin: a.hist = this evaluation's buffer; a.q = the pose's quaternion; a.tag = its sequence number)
   std::memcpy(a.R, h->last_R, sizeof(a.R));
   std::memcpy(a.t, h->last_t, sizeof(a.t));
-  a.gt_zero_buf = h->hist.idle();
-  a.gt_zero_words = h->hist.words();
+  a.gt.zero_buf = h->hist.idle();
+  a.gt.zero_words = h->hist.words();
   h->hist.idle_cleared_on(h->stream);  // cleared by this launch for the next evaluation
   h->fused_arrivals += uint64_t(h->nchunks);
   h->fused_launches += 1;

@@ -456,7 +456,7 @@ void fill_pass_args(const nidreg_handle* h, PassArgs& a, double* out_host = null
 void pose_from_se3(const double* se3, double* R, double* t);
 void remember_pose(nidreg_handle* h, const double* se3);
 int launch_hist_spline(nidreg_handle* h, const double* se3, bool alone = false);
-NearestFastArgs nearest_fast_args(const nidreg_handle* h, const double* T);
+NearestFast nearest_fast_args(const nidreg_handle* h, const double* T);
 int launch_hist_nearest(nidreg_handle* h, const double* T);
 int launch_entropy(nidreg_handle* h, double tag, bool tail = true, double* out_host = nullptr);
 bool grad_sums_table(nidreg_handle* h);

@@ -351,7 +351,7 @@ int group_eval(MultiGroup* g, const double* se3, bool want_grad, double* costs, 
   a.chunks = (h0->wide ? g->d_chunks_hist : g->d_chunks).as<Chunk>();
   a.nchunks = h0->wide ? g->nchunks_hist : g->nchunks;
   a.seg = h0->wide ? g->seg_hist : g->seg;
-  HIP_TRY(launch_spline_hist<double>(a));
+  HIP_TRY(launch_spline_hist(a));
   // entropy: NEB workgroups per pair -- none for small tables when every pair has gradient workgroups (they sum the table
   // themselves and clear the next evaluation's buffers, grad_sums_table)
   bool no_entropy_kernel = want_grad && grad_sums_table(h0);
@@ -364,8 +364,8 @@ int group_eval(MultiGroup* g, const double* se3, bool want_grad, double* costs, 
     a.nchunks = g->nchunks;
     a.seg = g->seg;
     a.lds_grad = g->lds_grad;
-    a.gt_from_partials = no_entropy_kernel ? 2 : 1;
-    HIP_TRY(launch_spline_grad<double>(a));
+    a.gt.from_partials = no_entropy_kernel ? 2 : 1;
+    HIP_TRY(launch_spline_grad(a));
     for (int i = 0; i < n; i++) {
       nidreg_handle* h = g->hs[size_t(i)];
       if (h->nchunks == 0 || h->num_points == 0) {  // an empty pair has no gradient workgroups: finalise (zeros) stand-alone
@@ -533,7 +533,7 @@ int group_eval_iso(MultiGroup* g, const double* T, double* costs) {
   a.chunks = g->d_chunks.as<Chunk>();
   a.nchunks = g->nchunks;
   a.seg = g->seg;
-  HIP_TRY(launch_nearest_hist<double>(a));
+  HIP_TRY(launch_nearest_hist(a));
   RC_TRY(launch_entropy_group(g, a.dyn));
   group_idle_cleared(g);
   for (int i = 0; i < n; i++) {

@@ -465,14 +465,14 @@ int plan_chunk_tables(nidreg_handle* h, const nidreg_desc& d) {
   if (d.mode == NIDREG_MODE_SPLINE) {
     PassArgs oa;
     fill_pass_args(h, oa);
-    const int og = occupancy_spline_grad<double>(oa);
-    const int oh = occupancy_spline_hist<double>(oa);
+    const int og = occupancy_spline_grad(oa);
+    const int oh = occupancy_spline_hist(oa);
     if (og > 0) per_cu_grad = std::min(og, 8);
     if (oh > 0) per_cu_hist = std::min(oh, 8);
   } else {  // NEAREST: the fast-tier kernels of the wide-angle models hold three (equirectangular) or four waves per SIMD
     PassArgs oa;
     fill_pass_args(h, oa);
-    const int on = occupancy_nearest_hist<double>(oa);
+    const int on = occupancy_nearest_hist(oa);
     if (on > 0) per_cu_grad = per_cu_hist = std::min(on, 4);
   }
   h->num_cus = num_cus;

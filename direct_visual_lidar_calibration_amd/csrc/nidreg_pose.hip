@@ -86,42 +86,23 @@ void estimate_direction_host(int model_id, const double* intr5, const double* di
 
 namespace {
 
-CamParams<double> pose_cam(int model, const double* intr, const double* dist) {
-  CamParams<double> c;
-  for (int i = 0; i < 5; i++) c.intr[i] = intr[i];
-  for (int i = 0; i < 8; i++) c.dist[i] = dist[i];
-  cam_derive<double>(model, c);
-  return c;
-}
-
-#define NID_POSE_MODEL_SWITCH(MACRO)                     \
-  switch (model) {                                       \
-    case MODEL_PLUMB_BOB: MACRO(MODEL_PLUMB_BOB); break; \
-    case MODEL_FISHEYE: MACRO(MODEL_FISHEYE); break;     \
-    case MODEL_OMNIDIR: MACRO(MODEL_OMNIDIR); break;     \
-    case MODEL_EQUIRECT: MACRO(MODEL_EQUIRECT); break;   \
-    case MODEL_ATAN: MACRO(MODEL_ATAN); break;           \
-    case MODEL_RATIONAL: MACRO(MODEL_RATIONAL); break;   \
-    default: return hipErrorInvalidValue;                \
-  }
-
 hipError_t launch_ransac_score(int model, const double* d_corr, int n, int tile, int ntiles, const double* d_Rs, int iterations, const CamParams<double>& cam, double thresh_sq,
                                int* d_counts) {
   const unsigned grid = unsigned((iterations + kPoseTileH - 1) / kPoseTileH) * unsigned(ntiles);
   const size_t lds = size_t(5) * size_t(tile) * sizeof(double);  // <= 40 KB
-#define NID_LAUNCH(M) hipLaunchKernelGGL((k_ransac_score<M>), dim3(grid), dim3(kPoseThreads), lds, nullptr, d_corr, n, tile, ntiles, d_Rs, iterations, cam, thresh_sq, d_counts)
-  NID_POSE_MODEL_SWITCH(NID_LAUNCH)
-#undef NID_LAUNCH
-  return hipGetLastError();
+  return with_model(model, hipErrorInvalidValue, [&](auto M) {
+    hipLaunchKernelGGL((k_ransac_score<M>), dim3(grid), dim3(kPoseThreads), lds, nullptr, d_corr, n, tile, ntiles, d_Rs, iterations, cam, thresh_sq, d_counts);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_ransac_flags(int model, const double* d_corr, int n, const double* d_Rs, const pose_u64* d_best, const CamParams<double>& cam, double thresh_sq,
                                unsigned char* d_flags, double* d_R_out) {
   const unsigned grid = unsigned((n + kPoseThreads - 1) / kPoseThreads);
-#define NID_LAUNCH(M) hipLaunchKernelGGL((k_ransac_flags<M>), dim3(grid), dim3(kPoseThreads), 0, nullptr, d_corr, n, d_Rs, d_best, cam, thresh_sq, d_flags, d_R_out)
-  NID_POSE_MODEL_SWITCH(NID_LAUNCH)
-#undef NID_LAUNCH
-  return hipGetLastError();
+  return with_model(model, hipErrorInvalidValue, [&](auto M) {
+    hipLaunchKernelGGL((k_ransac_flags<M>), dim3(grid), dim3(kPoseThreads), 0, nullptr, d_corr, n, d_Rs, d_best, cam, thresh_sq, d_flags, d_R_out);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace
@@ -205,7 +186,7 @@ int nidreg_estimate_rotation_ransac(int model_id, const double* intrinsics, cons
   int* const d_counts = reinterpret_cast<int*>(res + off_counts);
   unsigned char* const d_flags = reinterpret_cast<unsigned char*>(res + off_flags);
   const double* const d_corr = d_in.as<double>();
-  const CamParams<double> cam = pose_cam(model_id, intrinsics, distortion);
+  const CamParams<double> cam = make_cam(model_id, intrinsics, distortion);
   const double thresh_sq = error_thresh * error_thresh;
   const unsigned hgrid = unsigned((iterations + kPoseThreads - 1) / kPoseThreads);
   hipLaunchKernelGGL(k_ransac_hypotheses, dim3(hgrid), dim3(kPoseThreads), 0, nullptr, d_corr + 5 * sn, d_corr + 8 * sn, N, iterations, pose_u64(seed), d_pairs_in.as<int>(), d_Rs.as<double>());

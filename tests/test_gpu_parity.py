@@ -1734,3 +1734,98 @@ def test_fused_single_launch_other_shapes_and_its_fallback(monkeypatch):
     ok3, c3, g3 = h(x)
     assert c3 == c0 and np.array_equal(g3, g0)
     h.close()
+
+
+# What the host dispatch can select, as (bins, tuning, planner knobs, what info() must then report).  The knobs: NIDREG_MAX_SEGS=1
+# keeps every table on one column group per chunk (the straight-line kernels); eight workgroups over 256 columns with a free
+# segment (NIDREG_SEG_OVERHEAD=0, no minimum gain) cannot be had without chunks across groups (the SEG kernels).
+_STRAIGHT = {"NIDREG_MAX_SEGS": "1"}
+_ACROSS = {"NIDREG_SEG_OVERHEAD": "0", "NIDREG_SEG_MIN_GAIN": "0"}
+SPLINE_ROUTES = {
+    "wide_gw1": (256, {}, _STRAIGHT, {"lds_copies": 32, "columns_per_group": 1, "segmented": 0, "segmented_hist": 0}),
+    "wide_gw1_seg": (256, {"target_blocks": 8}, _ACROSS, {"lds_copies": 32, "columns_per_group": 1, "segmented": 1, "segmented_hist": 1}),
+    "generic_gw1": (256, {"lds_copies": 16}, _STRAIGHT, {"lds_copies": 16, "columns_per_group": 1, "segmented": 0, "segmented_hist": 0}),
+    "generic_gw1_seg": (256, {"lds_copies": 16, "target_blocks": 8}, _ACROSS, {"lds_copies": 16, "columns_per_group": 1, "segmented": 1, "segmented_hist": 0}),
+    "generic_gw4": (256, {"columns_per_group": 4}, {}, {"columns_per_group": 4, "segmented": 0, "segmented_hist": 0}),
+    "generic_b16": (16, {}, {"NIDREG_FUSED": "0"}, {"columns_per_group": 16, "segmented": 0, "fused": 0}),
+    "fused_full": (16, {}, {"NIDREG_FUSED_STASH": "full"}, {"fused": 1, "fused_full_stash": 1}),
+    "fused_uv": (16, {}, {"NIDREG_FUSED_STASH": "uv"}, {"fused": 1, "fused_full_stash": 0}),
+}
+NEAREST_ROUTES = {
+    "straight": ({}, _STRAIGHT, {"segmented": 0}),
+    "seg": ({"target_blocks": 8}, _ACROSS, {"segmented": 1}),
+}
+NEAREST_FAST_TIER = {"fisheye": 1, "equirectangular": 1, "atan": 0, "rational_polynomial": 0}  # (plumb_bob, omnidir: by field of view)
+
+
+@pytest.mark.parametrize("rec64", [False, True], ids=["rec32", "rec64"])
+@pytest.mark.parametrize("model", list(CAMERAS))
+def test_every_kernel_selection_of_the_host_dispatch_matches_the_oracle(model, rec64, monkeypatch):
+    """The launchers pick a kernel instantiation from (model, record type, WIDE, GW1, SEG, MULTI, fused stash); a wrong pick
+    -- Rec64 read as Rec32, WIDE and SEG swapped -- compiles and is invisible to everything but a run.  Every model x record
+    type goes through every selection here, on two small pairs (4096 and 3000 points: several chunks each): info() must report
+    the route the case means to take, a single evaluation meets the oracle at the bars of tests/parity.py, and the two pairs
+    as one grid (MULTI; never fused) give the sum of the single evaluations bit for bit (gradient: to rounding, and against the
+    summed oracle).  info() describes a handle's own tables, not a group's: the group's tables are built under the same
+    planner knobs (its first evaluation), which is what makes them straight or segmented, but that is not asserted."""
+    scenes = [scene_for(model, n=4096, seed=41), scene_for(model, n=3000, seed=42)]
+    clouds = []
+    for s in scenes:
+        pts = s.points.copy()
+        if rec64:
+            pts[:, :3] += 1e-9 * (1 + np.arange(pts.shape[0]))[:, None]  # no longer float32-exact
+        clouds.append(pts)
+    proj = nid.create_camera(scenes[0].model, scenes[0].intrinsics, scenes[0].distortion)
+    x = scenes[0].T_camera_lidar_init
+    refs = {}
+    for name, (bins, tuning, env, expect) in SPLINE_ROUTES.items():
+        if bins not in refs:
+            refs[bins] = [oracle_lib.nid_cost(s.model, s.intrinsics, s.distortion, s.image_f64, p, s.intensities, bins, x) for s, p in zip(scenes, clouds)]
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        hs = [nid.NIDCost(proj, s.image_f64, p, s.intensities, bins, **tuning) for s, p in zip(scenes, clouds)]
+        single = [h(x) for h in hs]
+        for h, (ok, c, g), ref in zip(hs, single, refs[bins]):
+            info = h.info()
+            assert info["float32_records"] == (0 if rec64 else 1), (name, info)
+            assert {k: info[k] for k in expect} == expect, (name, info)
+            assert ok and ref["ok"]
+            parity.check_cost(c, ref["cost"], what=name)
+            parity.check_grad(g, ref["grad"], what=name)
+        if not name.startswith("fused"):
+            multi = nid.MultiNIDCost(None)
+            for h in hs:
+                multi.add(h)
+            ok, c, g = multi(x)
+            assert ok and c == single[0][1] + single[1][1], (name, c, single)
+            assert np.allclose(g, single[0][2] + single[1][2], rtol=1e-11, atol=1e-14), name
+            parity.check_grad(g, refs[bins][0]["grad"] + refs[bins][1]["grad"], what=name + " multi")
+        for k in env:
+            monkeypatch.delenv(k)
+        for h in hs:
+            h.close()
+    # NEAREST: integer histogram bit for bit, single and as one grid (sum_costs)
+    s0 = scenes[0]
+    max_fov = oracle_lib.estimate_camera_fov(s0.model, s0.intrinsics, s0.distortion, s0.width, s0.height)
+    T = se3.to_matrix(x)
+    nrefs = [oracle_lib.cost_calculator_nid(s.model, s.intrinsics, s.distortion, s.image_u8, p, s.intensities, 256, max_fov, T, want_hist=True) for s, p in zip(scenes, clouds)]
+    for name, (tuning, env, expect) in NEAREST_ROUTES.items():
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        calcs = [nid.CostCalculatorNID(proj, s.image_u8, p, s.intensities, nid.NIDCostParams(256), max_fov=max_fov, **tuning) for s, p in zip(scenes, clouds)]
+        costs = []
+        for calc, (ref_cost, ref_hist) in zip(calcs, nrefs):
+            info = calc.info()
+            assert info["float32_records"] == (0 if rec64 else 1), (name, info)
+            assert {k: info[k] for k in expect} == expect, (name, info)
+            if model in NEAREST_FAST_TIER:
+                assert info["nearest_fast"] == NEAREST_FAST_TIER[model], (name, info)
+            costs.append(calc.calculate(T))
+            assert np.array_equal(calc.histogram_fixed()[0], ref_hist) and abs(costs[-1] - ref_cost) <= 1e-12, name
+        assert nid.sum_costs(calcs, T) == costs[0] + costs[1], name
+        for calc, (ref_cost, ref_hist) in zip(calcs, nrefs):
+            assert np.array_equal(calc.histogram_fixed()[0], ref_hist), name
+        for k in env:
+            monkeypatch.delenv(k)
+        for calc in calcs:
+            calc.close()
