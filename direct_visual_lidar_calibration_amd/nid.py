@@ -153,6 +153,17 @@ class Cloud:
             pass
 
 
+def _image_rows(image, dtype):
+    """The image as ``nidreg_create`` reads it (``image`` + ``image_row_stride``).  An array of the right dtype whose pixels are
+    contiguous within a row and whose rows lie a positive stride of at least one row apart -- a crop of a larger frame, rows
+    padded to an alignment -- is passed as it is, without a copy; anything else is copied into a contiguous array as before."""
+    dtype = np.dtype(dtype)
+    if (isinstance(image, np.ndarray) and image.dtype == dtype and image.ndim == 2 and image.shape[0] > 0 and image.shape[1] > 0
+            and image.strides[1] == dtype.itemsize and image.strides[0] >= image.shape[1] * dtype.itemsize):
+        return image
+    return np.ascontiguousarray(image, dtype=dtype)
+
+
 class _Handle:
     """RAII owner of one ``nidreg_handle`` (device residency of one LiDAR-camera pair)."""
 
@@ -172,10 +183,10 @@ class _Handle:
         if intensities.shape != (points.shape[0],):
             raise ValueError("intensities must be (N,)")
         if mode == _lib.MODE_SPLINE:
-            image = np.ascontiguousarray(image, dtype=np.float64)
+            image = _image_rows(image, np.float64)  # (this name keeps the caller's array alive until nidreg_create has returned)
             image_dtype = _lib.IMAGE_F64
         else:
-            image = np.ascontiguousarray(image, dtype=np.uint8)
+            image = _image_rows(image, np.uint8)
             image_dtype = _lib.IMAGE_U8
         d = _lib.NidregDesc()
         d.struct_size = ctypes.sizeof(_lib.NidregDesc)
@@ -505,7 +516,7 @@ class CostCalculatorNID(_Handle):
 
     def __init__(self, proj, image, points, intensities, params=None, max_fov=None, device=0, precision="fp64", **tuning):
         params = params or NIDCostParams()
-        image = np.ascontiguousarray(image, dtype=np.uint8)
+        image = _image_rows(image, np.uint8)
         if max_fov is None:
             max_fov = estimate_camera_fov(proj, (image.shape[1], image.shape[0]), device=device)
         self.max_fov = float(max_fov)
@@ -515,7 +526,7 @@ class CostCalculatorNID(_Handle):
     def from_cloud(cls, proj, image, cloud, params=None, max_fov=None, cull=None, precision="fp64", **tuning):
         """``cull -> new CostCalculatorNID`` (visual_camera_calibration.cpp:76-85) fused on the device."""
         params = params or NIDCostParams()
-        image = np.ascontiguousarray(image, dtype=np.uint8)
+        image = _image_rows(image, np.uint8)
         if max_fov is None:
             max_fov = estimate_camera_fov(proj, (image.shape[1], image.shape[0]), device=cloud.device)
         self = cls.__new__(cls)

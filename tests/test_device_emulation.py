@@ -21,6 +21,8 @@ CAMERAS = {
     "equirectangular": ("equirectangular", [384.0, 256.0], [], 384, 256),
     "atan": ("atan", [210.0, 205.0, 160.0, 120.0], [0.6], 320, 240),
     "rational_polynomial": ("rational_polynomial", [210.0, 205.0, 160.0, 120.0], [0.05, -0.02, 1e-4, -2e-4, 0.01, 0.03, -0.01, 0.002], 320, 240),
+    # W % 4 = 3, H % 4 = 1: the pitch rounding and the partial last strip of the bin image (tests/test_bin_image_edges.py on the GPU)
+    "plumb_bob_323x241": ("plumb_bob", [210.0, 205.0, 161.5, 120.5], [-0.04, 0.08, 1e-4, -3e-4, -0.04], 323, 241),
 }
 EXE = os.path.join(ROOT, "tests", "cxx", "emulate_device_path.bin")
 
@@ -32,7 +34,7 @@ def exe():
     return EXE
 
 
-@pytest.mark.parametrize("model,bins", [("plumb_bob", 16), ("plumb_bob", 256), ("fisheye", 64), ("omnidir", 16), ("equirectangular", 256), ("atan", 16), ("rational_polynomial", 100)])
+@pytest.mark.parametrize("model,bins", [("plumb_bob", 16), ("plumb_bob", 256), ("fisheye", 64), ("omnidir", 16), ("equirectangular", 256), ("atan", 16), ("rational_polynomial", 100), ("plumb_bob_323x241", 16)])
 def test_device_algorithm_on_host_matches_oracle(exe, tmp_path, model, bins):
     s = synth.make_scene(CAMERAS[model], num_points=20000, seed=17)
     x = np.asarray(s.T_camera_lidar_init, dtype=np.float64)
