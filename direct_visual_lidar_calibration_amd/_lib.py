@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("NIDREG_LIB", os.path.join(CSRC_DIR, "libnidreg.so"))
 NIDREG_OK = 0
 NIDREG_FALSE = 1
 NIDREG_ERR_INVALID = -1
+NIDREG_ERR_FULL = -4
 NIDREG_OUT_DOUBLES = 16
 
 MODE_SPLINE, MODE_NEAREST = 0, 1
@@ -72,6 +73,8 @@ EXPORTS = [
     "nidreg_estimate_directions", "nidreg_ransac_sample_pairs", "nidreg_estimate_rotation_ransac",
     "nidreg_integrator_create", "nidreg_integrator_insert", "nidreg_integrator_insert_f32", "nidreg_integrator_insert_cloud2", "nidreg_integrator_size", "nidreg_integrator_get", "nidreg_integrator_info",
     "nidreg_integrator_destroy",
+    "nidreg_odom_create", "nidreg_odom_destroy", "nidreg_odom_knn_covariances", "nidreg_odom_covariances", "nidreg_odom_model_insert", "nidreg_odom_model_info", "nidreg_odom_model_get",
+    "nidreg_odom_set_source", "nidreg_odom_linearize", "nidreg_odom_error", "nidreg_odom_correspondences", "nidreg_odom_deskew_insert",
 ]
 
 _lib = None
@@ -151,6 +154,20 @@ def load():
     lib.nidreg_integrator_info.argtypes = [ctypes.c_void_p, c_int64_p]
     lib.nidreg_integrator_destroy.restype = None
     lib.nidreg_integrator_destroy.argtypes = [ctypes.c_void_p]
+    c_int32_p = ctypes.POINTER(ctypes.c_int32)
+    lib.nidreg_odom_create.argtypes = [ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]
+    lib.nidreg_odom_destroy.restype = None
+    lib.nidreg_odom_destroy.argtypes = [ctypes.c_void_p]
+    lib.nidreg_odom_knn_covariances.argtypes = [ctypes.c_void_p, c_double_p, ctypes.c_int32, ctypes.c_int32, c_int32_p, c_double_p, c_double_p]
+    lib.nidreg_odom_covariances.argtypes = [ctypes.c_void_p, c_double_p, ctypes.c_int32, ctypes.c_int32, c_int32_p, c_double_p, c_double_p]
+    lib.nidreg_odom_model_insert.argtypes = [ctypes.c_void_p, c_double_p, c_double_p, ctypes.c_int32]
+    lib.nidreg_odom_model_info.argtypes = [ctypes.c_void_p, c_int64_p]
+    lib.nidreg_odom_model_get.argtypes = [ctypes.c_void_p, c_int32_p, c_double_p, c_double_p]
+    lib.nidreg_odom_set_source.argtypes = [ctypes.c_void_p, c_double_p, c_double_p, c_int32_p, ctypes.c_int32]
+    lib.nidreg_odom_linearize.argtypes = [ctypes.c_void_p, c_double_p, ctypes.c_int32, ctypes.c_double, c_double_p]
+    lib.nidreg_odom_error.argtypes = [ctypes.c_void_p, c_double_p, ctypes.c_int32, c_double_p]
+    lib.nidreg_odom_correspondences.argtypes = [ctypes.c_void_p, c_int32_p, c_double_p, c_double_p]
+    lib.nidreg_odom_deskew_insert.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_int32] * 9 + [ctypes.c_double] * 3 + [c_double_p] * 3 + [c_int64_p]
     lib.nidreg_rccl_unique_id.argtypes = [ctypes.c_char_p]
     lib.nidreg_shard_comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]
     lib.nidreg_shard_attach_rccl.argtypes = [ctypes.c_void_p, ctypes.c_void_p]

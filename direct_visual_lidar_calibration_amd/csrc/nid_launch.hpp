@@ -102,6 +102,14 @@ hipError_t launch_lidar_image(int model, const double* intr, const double* dist,
 // preprocess.cpp:464-473 rank equalisation in place on a device array (nid_build.hip; synchronises the stream)
 hipError_t equalize_intensities_device(double* d_intensities, long long n, hipStream_t stream);
 
+// the PointCloud2 route of the voxel integrator in two halves (nidreg_voxel.hip), for a caller that puts its own kernel between them
+// (nidreg_odom_deskew_insert): argument checks + upload of the raw records and room for the decoded frame (num_points == 0: nothing
+// is staged), then the insert of the num_points x double4 points / num_points x double intensities written there
+struct VoxCloud2;
+int integrator_stage_cloud2(nidreg_integrator* h, const char* who, const void* data, int64_t num_points, int32_t point_step, int32_t x_offset, int32_t y_offset, int32_t z_offset,
+                            int32_t xyz_datatype, int32_t intensity_offset, int32_t intensity_datatype, VoxCloud2* cloud, double4** d_pts, double** d_int);
+int integrator_insert_staged(nidreg_integrator* h, const char* who, int64_t num_points, int64_t* num_skipped);
+
 // error text of the calling thread (nidreg_last_error); returns `code`
 int fail(int code, const std::string& msg);
 

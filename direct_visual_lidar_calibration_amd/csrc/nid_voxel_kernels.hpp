@@ -24,6 +24,7 @@
 // slot is empty, so a fresh table is one memset.
 // ORDER of nidreg_integrator_get: ascending sequence number of the voxels' winners (the reference's is std::unordered_map
 // iteration order, i.e. unspecified); deterministic and identical from run to run.
+// (The kernels that are not templates are `static`: nidreg_odom.hip includes this header too.)
 // At map resolution nearly every point claims a slot of its own: the atomics have distinct destinations, there is nothing to
 // aggregate on chip first, and the kernels are bound by the latency of random 32-byte accesses (slot = key, sequence number and
 // payload in ONE 32-byte sector).  Compiled with -ffp-contract=off: +, *, /, sqrt, floor as the host's.
@@ -223,7 +224,7 @@ __global__ __launch_bounds__(kVoxThreads) void k_vox_decode_cloud2(VoxCloud2 c, 
   }
 }
 
-__global__ __launch_bounds__(kVoxThreads) void k_vox_rehash(const VoxSlot* old_slots, long long old_cap, VoxSlot* slots, unsigned mask) {
+static __global__ __launch_bounds__(kVoxThreads) void k_vox_rehash(const VoxSlot* old_slots, long long old_cap, VoxSlot* slots, unsigned mask) {
   const long long stride = (long long)gridDim.x * kVoxThreads;
   for (long long s = (long long)blockIdx.x * kVoxThreads + threadIdx.x; s < old_cap; s += stride) {
     const VoxSlot v = old_slots[s];
@@ -236,7 +237,7 @@ __global__ __launch_bounds__(kVoxThreads) void k_vox_rehash(const VoxSlot* old_s
 }
 
 // (seq + 1, slot) of every occupied slot, in arrival order -- the sort that follows fixes the order; *count += their number
-__global__ __launch_bounds__(kVoxThreads) void k_vox_compact(const VoxSlot* slots, long long cap, vox_u64* count, vox_u64* seq_out, unsigned* slot_out) {
+static __global__ __launch_bounds__(kVoxThreads) void k_vox_compact(const VoxSlot* slots, long long cap, vox_u64* count, vox_u64* seq_out, unsigned* slot_out) {
   const long long stride = (long long)gridDim.x * kVoxThreads;
   for (long long s = (long long)blockIdx.x * kVoxThreads + threadIdx.x; s < cap; s += stride) {
     if (slots[s].key == 0) continue;
@@ -246,7 +247,7 @@ __global__ __launch_bounds__(kVoxThreads) void k_vox_compact(const VoxSlot* slot
   }
 }
 
-__global__ __launch_bounds__(kVoxThreads) void k_vox_gather(const VoxSlot* slots, const vox_u64* seq_sorted, const unsigned* slot_sorted, long long m, float4* rec_out, long long* seq_out) {
+static __global__ __launch_bounds__(kVoxThreads) void k_vox_gather(const VoxSlot* slots, const vox_u64* seq_sorted, const unsigned* slot_sorted, long long m, float4* rec_out, long long* seq_out) {
   const long long stride = (long long)gridDim.x * kVoxThreads;
   for (long long j = (long long)blockIdx.x * kVoxThreads + threadIdx.x; j < m; j += stride) {
     rec_out[j] = slots[slot_sorted[j]].rec;

@@ -156,6 +156,48 @@ void cloud2_launch(const VoxCloud2& c, int32_t intensity_datatype, double4* pts,
 }
 
 }  // namespace
+
+// the two halves of the PointCloud2 route around the decode kernel, shared with nidreg_odom_deskew_insert (nidreg_odom.hip): the
+// argument checks and the upload of the records as they lie in the message ...
+int integrator_stage_cloud2(nidreg_integrator* h, const char* who, const void* data, int64_t num_points, int32_t point_step, int32_t x_offset, int32_t y_offset, int32_t z_offset,
+                            int32_t xyz_datatype, int32_t intensity_offset, int32_t intensity_datatype, VoxCloud2* cloud, double4** d_pts_out, double** d_int_out) {
+  if (!h) return fail(NIDREG_ERR_INVALID, std::string(who) + ": null integrator");
+  if (num_points < 0 || (num_points > 0 && !data)) return fail(NIDREG_ERR_INVALID, std::string(who) + ": negative num_points or null data");
+  if (point_step < 1 || point_step > 65535) return fail(NIDREG_ERR_INVALID, std::string(who) + ": point_step must lie in 1..65535");
+  if (xyz_datatype != kPcFloat32 && xyz_datatype != kPcFloat64)
+    return fail(NIDREG_ERR_INVALID, std::string(who) + ": x, y and z must all be FLOAT32 (7) or all FLOAT64 (8), got datatype " + std::to_string(xyz_datatype));
+  const int xyz_bytes = cloud2_type_bytes(xyz_datatype), int_bytes = cloud2_type_bytes(intensity_datatype);
+  if (!int_bytes) return fail(NIDREG_ERR_INVALID, std::string(who) + ": the intensity must be UINT8, UINT16, UINT32, FLOAT32 or FLOAT64, got datatype " + std::to_string(intensity_datatype));
+  for (const int32_t off : {x_offset, y_offset, z_offset})
+    if (off < 0 || off > point_step - xyz_bytes) return fail(NIDREG_ERR_INVALID, std::string(who) + ": a coordinate field lies outside the point_step bytes of a record");
+  if (intensity_offset < 0 || intensity_offset > point_step - int_bytes) return fail(NIDREG_ERR_INVALID, std::string(who) + ": the intensity field lies outside the point_step bytes of a record");
+  if (num_points == 0) return NIDREG_OK;
+  if (num_points > INT64_MAX / 65535) return fail(NIDREG_ERR_INVALID, std::string(who) + ": num_points x point_step overflows");
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t bytes = size_t(num_points) * size_t(point_step);
+  const size_t room = (bytes + 15) & ~size_t(15);  // the staging loads of k_vox_decode_cloud2 end on a 16-byte boundary
+  if (h->raw_bytes < room) {
+    HIP_TRY(h->d_raw.alloc(room));
+    h->raw_bytes = room;
+  }
+  if (const int rc = vox_frame_room(h, size_t(num_points) * 40)) return rc;
+  HIP_TRY(hipMemcpy(h->d_raw.as<void>(), data, bytes, hipMemcpyHostToDevice));  // the records as they lie in the message
+  unsigned char* const d = h->d_frame.as<unsigned char>();
+  *d_pts_out = reinterpret_cast<double4*>(d);
+  *d_int_out = reinterpret_cast<double*>(d + size_t(num_points) * 32);
+  *cloud = VoxCloud2{h->d_raw.as<const unsigned char>(), (long long)num_points, point_step, x_offset, y_offset, z_offset, intensity_offset};
+  return NIDREG_OK;
+}
+
+// ... and the insert of the double frame a kernel has written where integrator_stage_cloud2 said
+int integrator_insert_staged(nidreg_integrator* h, const char* who, int64_t num_points, int64_t* num_skipped) {
+  unsigned char* const d = h->d_frame.as<unsigned char>();
+  int64_t skipped = 0;
+  const int rc = vox_insert(h, who, VoxFrameF64{reinterpret_cast<const double4*>(d), reinterpret_cast<const double*>(d + size_t(num_points) * 32)}, num_points, &skipped);
+  if (num_skipped) *num_skipped = skipped;
+  return rc;
+}
+
 }  // namespace nidreg
 
 using namespace nidreg;
@@ -236,40 +278,17 @@ int nidreg_integrator_insert_cloud2(nidreg_integrator* h, const void* data, int6
                                     int32_t intensity_offset, int32_t intensity_datatype, int64_t* num_skipped) {
   const char* const who = "nidreg_integrator_insert_cloud2";
   if (num_skipped) *num_skipped = 0;
-  if (!h) return fail(NIDREG_ERR_INVALID, std::string(who) + ": null integrator");
-  if (num_points < 0 || (num_points > 0 && !data)) return fail(NIDREG_ERR_INVALID, std::string(who) + ": negative num_points or null data");
-  if (point_step < 1 || point_step > 65535) return fail(NIDREG_ERR_INVALID, std::string(who) + ": point_step must lie in 1..65535");
-  if (xyz_datatype != kPcFloat32 && xyz_datatype != kPcFloat64)
-    return fail(NIDREG_ERR_INVALID, std::string(who) + ": x, y and z must all be FLOAT32 (7) or all FLOAT64 (8), got datatype " + std::to_string(xyz_datatype));
-  const int xyz_bytes = cloud2_type_bytes(xyz_datatype), int_bytes = cloud2_type_bytes(intensity_datatype);
-  if (!int_bytes) return fail(NIDREG_ERR_INVALID, std::string(who) + ": the intensity must be UINT8, UINT16, UINT32, FLOAT32 or FLOAT64, got datatype " + std::to_string(intensity_datatype));
-  for (const int32_t off : {x_offset, y_offset, z_offset})
-    if (off < 0 || off > point_step - xyz_bytes) return fail(NIDREG_ERR_INVALID, std::string(who) + ": a coordinate field lies outside the point_step bytes of a record");
-  if (intensity_offset < 0 || intensity_offset > point_step - int_bytes) return fail(NIDREG_ERR_INVALID, std::string(who) + ": the intensity field lies outside the point_step bytes of a record");
+  VoxCloud2 c;
+  double4* d_pts = nullptr;
+  double* d_int = nullptr;
+  if (const int rc = integrator_stage_cloud2(h, who, data, num_points, point_step, x_offset, y_offset, z_offset, xyz_datatype, intensity_offset, intensity_datatype, &c, &d_pts, &d_int)) return rc;
   if (num_points == 0) return NIDREG_OK;
-  if (num_points > INT64_MAX / 65535) return fail(NIDREG_ERR_INVALID, std::string(who) + ": num_points x point_step overflows");
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t bytes = size_t(num_points) * size_t(point_step);
-  const size_t room = (bytes + 15) & ~size_t(15);  // the staging loads of k_vox_decode_cloud2 end on a 16-byte boundary
-  if (h->raw_bytes < room) {
-    HIP_TRY(h->d_raw.alloc(room));
-    h->raw_bytes = room;
-  }
-  if (const int rc = vox_frame_room(h, size_t(num_points) * 40)) return rc;
-  HIP_TRY(hipMemcpy(h->d_raw.as<void>(), data, bytes, hipMemcpyHostToDevice));  // the records as they lie in the message
-  unsigned char* const d = h->d_frame.as<unsigned char>();
-  double4* const d_pts = reinterpret_cast<double4*>(d);
-  double* const d_int = reinterpret_cast<double*>(d + size_t(num_points) * 32);
-  const VoxCloud2 c{h->d_raw.as<const unsigned char>(), (long long)num_points, point_step, x_offset, y_offset, z_offset, intensity_offset};
   if (xyz_datatype == kPcFloat32)
     cloud2_launch<kPcFloat32>(c, intensity_datatype, d_pts, d_int);
   else
     cloud2_launch<kPcFloat64>(c, intensity_datatype, d_pts, d_int);
   HIP_TRY(hipGetLastError());
-  int64_t skipped = 0;
-  const int rc = vox_insert(h, who, VoxFrameF64{d_pts, d_int}, num_points, &skipped);
-  if (num_skipped) *num_skipped = skipped;
-  return rc;
+  return integrator_insert_staged(h, who, num_points, num_skipped);
 }
 
 int nidreg_integrator_size(nidreg_integrator* h, int64_t* num_voxels) {

@@ -33,6 +33,35 @@ def _check(rc, what):
     return _lib.check(rc, what)
 
 
+def cloud2_layout(msg_or_fields, intensity_channel, who="insert_cloud2"):
+    """What the PointCloud2 routes need of a message (``StaticPointCloudIntegrator.insert_cloud2`` says which forms it may have):
+    ``(data uint8 array, number of points, point_step, {field name: (offset, datatype)})``, after the checks they share."""
+    get = msg_or_fields.get if isinstance(msg_or_fields, dict) else lambda k, d=None: getattr(msg_or_fields, k, d)
+    table = {}
+    for f in get("fields"):
+        name, offset, datatype = (f[0], f[1], f[2]) if isinstance(f, (tuple, list)) else (f.name, f.offset, f.datatype)
+        table[name] = (int(offset), int(datatype))  # (a name listed twice keeps its last entry, as in the reference)
+    if get("is_bigendian"):
+        raise ValueError(f"{who}: big-endian point data is not read")
+    for k in ("x", "y", "z"):
+        if k not in table:
+            raise ValueError(f"{who}: the cloud has no '{k}' field (fields: {', '.join(table)})")
+    if intensity_channel not in table:
+        raise ValueError(f"{who}: the cloud has no '{intensity_channel}' field to take intensities from (fields: {', '.join(table)})")
+    if not (table["x"][1] == table["y"][1] == table["z"][1]):
+        raise ValueError(f"{who}: x, y and z have different datatypes")
+    n = get("num_points")
+    n = int(get("width")) * int(get("height")) if n is None else int(n)
+    step = int(get("point_step"))
+    data = get("data")
+    data = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
+    if data.dtype != np.uint8 or data.ndim != 1 or not data.flags.c_contiguous:
+        raise ValueError(f"{who}: data must be a contiguous run of bytes")
+    if n < 0 or step < 1 or data.size < n * step:
+        raise ValueError(f"{who}: {data.size} data bytes for {n} points of {step} bytes")
+    return data, n, step, table
+
+
 class StaticPointCloudIntegrator:
     """``vlcal::StaticPointCloudIntegrator``: one entry per occupied voxel, the LAST point inserted into it (the reference
     overwrites, static_point_cloud_integrator.cpp:35).  Defaults as the reference's (:8-12).
@@ -81,29 +110,7 @@ class StaticPointCloudIntegrator:
         least width x height x point_step bytes), ``width`` and ``height`` (or ``num_points``), ``is_bigendian``.  Returns the
         number of points skipped for a non-finite coordinate; they still take a sequence number.  Missing x / y / z, a missing
         intensity channel, mixed or unsupported datatypes and big-endian data raise ``ValueError``."""
-        get = msg_or_fields.get if isinstance(msg_or_fields, dict) else lambda k, d=None: getattr(msg_or_fields, k, d)
-        table = {}
-        for f in get("fields"):
-            name, offset, datatype = (f[0], f[1], f[2]) if isinstance(f, (tuple, list)) else (f.name, f.offset, f.datatype)
-            table[name] = (int(offset), int(datatype))  # (a name listed twice keeps its last entry, as in the reference)
-        if get("is_bigendian"):
-            raise ValueError("insert_cloud2: big-endian point data is not read")
-        for k in ("x", "y", "z"):
-            if k not in table:
-                raise ValueError(f"insert_cloud2: the cloud has no '{k}' field (fields: {', '.join(table)})")
-        if intensity_channel not in table:
-            raise ValueError(f"insert_cloud2: the cloud has no '{intensity_channel}' field to take intensities from (fields: {', '.join(table)})")
-        if not (table["x"][1] == table["y"][1] == table["z"][1]):
-            raise ValueError("insert_cloud2: x, y and z have different datatypes")
-        n = get("num_points")
-        n = int(get("width")) * int(get("height")) if n is None else int(n)
-        step = int(get("point_step"))
-        data = get("data")
-        data = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
-        if data.dtype != np.uint8 or data.ndim != 1 or not data.flags.c_contiguous:
-            raise ValueError("insert_cloud2: data must be a contiguous run of bytes")
-        if n < 0 or step < 1 or data.size < n * step:
-            raise ValueError(f"insert_cloud2: {data.size} data bytes for {n} points of {step} bytes")
+        data, n, step, table = cloud2_layout(msg_or_fields, intensity_channel)
         skipped = ctypes.c_int64()
         rc = self._lib.nidreg_integrator_insert_cloud2(self._h, data.ctypes.data if n else None, n, step, table["x"][0], table["y"][0], table["z"][0], table["x"][1],
                                                        table[intensity_channel][0], table[intensity_channel][1], ctypes.byref(skipped))
@@ -232,7 +239,8 @@ class TimeKeeper:
     """``vlcal::TimeKeeper::process`` (time_keeper.cpp:44-160) with the default ``AbsPointTimeParams`` (time_keeper.hpp:13-16:
     both true), reduced to what decides whether a frame is kept: the frame's stamp after ``replace_points_stamp``, which reads
     only the first, the last and the smallest per-point time.  The per-point times themselves are used by the dynamic
-    integrator alone and are not rewritten here.  Warnings go to ``log`` once, as the reference's ``first_warning``."""
+    integrator alone: ``process_times`` returns them as an affine map of the raw column, which the GPU applies to the raw field.
+    Warnings go to ``log`` once, as the reference's ``first_warning``."""
 
     def __init__(self, log=None):
         self.log = log if log is not None else (lambda msg: print(msg, file=sys.stderr))
@@ -240,6 +248,9 @@ class TimeKeeper:
         self.last_points_stamp = -1.0
         self.point_time_offset = 0.0
         self.stamp = None  # the stamp of the last processed frame after replacement
+        self.num_scans = 0  # estimate_scan_duration (:162-180), used by process_times alone
+        self.first_points_stamp = 0.0
+        self.estimated_scan_duration = -1.0
 
     def process(self, stamp, first=None, last=None, min_time=None):
         """``stamp`` [s]; ``first`` / ``last`` / ``min_time``: per-point times of the first and last point and their minimum
@@ -259,6 +270,46 @@ class TimeKeeper:
             self.log(f"       : current:{stamp:.6f} last:{self.last_points_stamp:.6f} diff:{diff:.6f}")
         self.last_points_stamp = stamp
         return True
+
+    def process_times(self, stamp, first=None, last=None, min_time=None, raw_scale=1.0):
+        """``process`` and, with it, the per-point times ``replace_points_stamp`` leaves (:64-160) as an affine map of the raw
+        time column: returns ``(keep, scale, shift)`` with ``time[i] = raw[i] * scale + shift`` [s].  ``first`` / ``last`` /
+        ``min_time`` are ``raw * raw_scale`` (``raw_scale`` = 1e-9 for the nanoseconds of a uint32 field).  Without a time field
+        (``first=None``) the times are the pseudo times ``scale * i / n`` with ``scale`` the estimated scan duration -- 0 for the
+        first frame, whose times are all zero."""
+        if first is None:
+            duration = self._estimate_scan_duration(float(stamp))
+            return self.process(stamp), (duration if duration > 0.0 else 0.0), 0.0
+        cache = []
+
+        def min_once():
+            if not cache:
+                cache.append(float(min_time() if callable(min_time) else min_time))
+            return cache[0]
+
+        scale, shift = float(raw_scale), 0.0
+        f, l = float(first), float(last)
+        if f < 0.0 or l < 0.0:  # :92-103
+            shift -= min_once()
+            f -= min_once()
+        if f >= 1.0:  # :106-157: absolute times
+            if f > 1e16:  # :118-128
+                scale, shift, f = scale * 1e-9, shift * 1e-9, f * 1e-9
+            shift -= f  # :153-156
+        return self.process(stamp, first, last, min_once), scale, shift
+
+    def _estimate_scan_duration(self, stamp):
+        if self.estimated_scan_duration > 0.0:
+            return self.estimated_scan_duration
+        self.num_scans += 1
+        if self.num_scans == 1:
+            self.first_points_stamp = stamp
+            return -1.0
+        duration = (stamp - self.first_points_stamp) / (self.num_scans - 1)
+        if self.num_scans == 1000:
+            self.log(f"estimated scan duration:{duration}")
+            self.estimated_scan_duration = duration
+        return duration
 
     def _replace_points_stamp(self, stamp, first, last, min_time):
         if first is None:  # :67-83: pseudo per-point times; the stamp stays

@@ -1,0 +1,53 @@
+"""``preprocess -d`` on the MI355X engine, from ROS1 bags: the LiDAR is carried through the scene, every scan is registered against a
+running model with continuous-time GICP and deskewed, and all raw points go into the voxel grid (``odometry``).
+
+    python -m direct_visual_lidar_calibration_amd.preprocess_dynamic bags/ data/ -a
+    python -m direct_visual_lidar_calibration_amd.preprocess_dynamic bags/ data/ -a --target_num_points 10000 --k_neighbors 20 --seed 0
+
+``preprocess_ros1.run`` with ``odometry.DynamicPointCloudIntegrator`` in the place of the static integrator: the same options, topics,
+camera parameters, per-bag outputs and ``calib.json`` (``preprocess_ros1`` lists the differences from the reference; ``odometry`` those of
+the integrator).  ``--k_neighbors`` is used here; ``--target_num_points`` and ``--seed`` (the scan sampler's) are extensions: the reference
+fixes 10000 and seeds ``std::mt19937`` by default.  ``-d`` is accepted and implied.  ``--min_distance`` is honoured, in the odometry frame.
+"""
+import functools
+import sys
+
+from . import odometry, preprocess_ros1
+from .preprocess_map import _attach_values
+
+
+def build_parser():
+    p = preprocess_ros1.build_parser()
+    p.prog = "preprocess_dynamic"
+    p.description = "preprocess with dynamic LiDAR integration"
+    p.add_argument("--target_num_points", type=int, default=10000, help="points a scan is sampled down to for the registration")
+    p.add_argument("--seed", type=int, default=0, help="seed of the scan sampler")
+    return p
+
+
+def run(args, **kw):
+    if args.k_neighbors < 2 or args.k_neighbors > 32:
+        raise ValueError(f"error: --k_neighbors {args.k_neighbors}: 2..32 neighbours are supported")
+    if args.target_num_points < args.k_neighbors:
+        raise ValueError(f"error: --target_num_points {args.target_num_points} is below --k_neighbors {args.k_neighbors}")
+    factory = functools.partial(odometry.DynamicPointCloudIntegrator, k_neighbors=args.k_neighbors, target_num_points=args.target_num_points, seed=args.seed)
+    return preprocess_ros1.run(args, integrator_factory=factory, **kw)
+
+
+def main(argv=None):
+    parser = build_parser()
+    args = parser.parse_args(_attach_values(sys.argv[1:] if argv is None else list(argv)))
+    if args.data_path is None or args.dst_path is None:
+        parser.print_help()
+        return 0
+    try:
+        run(args)
+    except (OSError, ValueError, odometry.ModelFullError) as e:
+        msg = str(e)
+        print(msg if msg.startswith("error:") else f"error: {msg}", file=sys.stderr)
+        return 1
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -15,7 +15,8 @@ then the LiDAR's field of view from the first bag, both LiDAR images of every ba
 The bag reader is ``rosbag1`` (pure Python, no ROS); a frame's records are uploaded as they lie in the message and decoded on the
 GPU (``StaticPointCloudIntegrator.insert_cloud2``).  Differences from the reference:
 
-* ``-d / --dynamic_lidar_integration`` (CT-GICP) is not built here: status 1 and a message;
+* ``-d / --dynamic_lidar_integration`` is refused here with status 1 and a message: the dynamic LiDAR integration (CT-GICP) is a
+  command of its own, ``preprocess_dynamic``, which runs this module's ``run`` with ``odometry.DynamicPointCloudIntegrator``;
 * ROS2 bags (sqlite3 / mcap) are not read: a file that does not start with ``#ROSBAG V2.0`` is not a bag (``valid_bag``);
 * images: ``sensor_msgs/Image`` in mono8 / bgr8 / rgb8 / bgra8 / rgba8 and PNG ``sensor_msgs/CompressedImage``; JPEG is refused;
 * where the reference dereferences a null message -- a cloud without x / y / z or without the intensity channel, a bag without the
@@ -25,7 +26,7 @@ GPU (``StaticPointCloudIntegrator.insert_cloud2``).  Differences from the refere
   [-2^20, 2^20) is refused; the output order of the points is ascending sequence number of the winners;
 * an empty ``--camera_distortion_coeffs`` string means no coefficients (the reference's ``std::stod("")`` throws);
 * ``--visualize`` is not offered; ``--device`` is an extension; ``--k_neighbors`` and ``--verbose`` are accepted and unused (they
-  configure the dynamic integrator).
+  configure the dynamic integrator: ``preprocess_dynamic``).
 """
 import argparse
 import os
@@ -51,7 +52,7 @@ def build_parser():
     p.add_argument("--bag_id", type=int, help="specify the bag to use (just for evaluation)")
     p.add_argument("--first_n_bags", type=int, help="use only the first N bags (just for evaluation)")
     p.add_argument("-a", "--auto_topic", action="store_true", help="automatically select topics")
-    p.add_argument("-d", "--dynamic_lidar_integration", action="store_true", help="create target point cloud from dynamic LiDAR data (not built here: refused)")
+    p.add_argument("-d", "--dynamic_lidar_integration", action="store_true", help="create target point cloud from dynamic LiDAR data (refused here: use preprocess_dynamic)")
     p.add_argument("-i", "--intensity_channel", default="auto", help="auto or channel name")
     p.add_argument("--camera_info_topic")
     p.add_argument("--image_topic")
@@ -161,15 +162,21 @@ def get_camera_params(args, bag, camera_info_topic, image_topic, log=print):
     return model, size, intrinsics, distortion
 
 
+def time_field(cloud):
+    """The cloud's per-point time field (ros_cloud_converter.hpp:81-84: the last one listed of ``TIME_FIELDS``), or ``None``"""
+    field = None
+    for f in cloud.fields:
+        if f.name in TIME_FIELDS:
+            field = f
+    return field
+
+
 def frame_times(cloud, where):
     """What ``TimeKeeper.process`` needs of a frame (extract_raw_points, ros_cloud_converter.hpp:121-142): ``(stamp, first, last,
     min)`` with ``first`` = ``None`` when the cloud has no time field or no points; ``min`` is a callable (one pass over the column,
     run only if a time is negative).  uint32 times are nanoseconds (``/ 1e9``)."""
     stamp = rosbag1.stamp_to_sec(cloud.stamp)
-    field = None
-    for f in cloud.fields:
-        if f.name in TIME_FIELDS:
-            field = f
+    field = time_field(cloud)
     n = rosbag1.num_points(cloud)
     if field is None or n == 0:
         return stamp, None, None, None
@@ -184,8 +191,11 @@ def frame_times(cloud, where):
 
 def integrate_bag(args, bag, points_topic, intensity_channel, integrator, warn=_warn):
     """:442-460: every PointCloud2 message of the topic, in the view's order, through the time keeper and into the integrator.
-    Returns ``(frames inserted, frames skipped for a rewinding stamp, points skipped for a non-finite coordinate)``."""
+    Returns ``(frames inserted, frames skipped for a rewinding stamp, points skipped for a non-finite coordinate)``.  An integrator
+    with ``insert_cloud2_timed`` (the dynamic one) also gets the frame's per-point times, as the time field and the affine map of
+    ``TimeKeeper.process_times``."""
     keeper = preprocess.TimeKeeper(log=warn)
+    timed = getattr(integrator, "insert_cloud2_timed", None)
     inserted = rewound = nonfinite = 0
     for k, m in enumerate(bag.messages(points_topic)):
         where = f"(message {k} of points topic '{points_topic}' in {bag.path})"
@@ -201,12 +211,21 @@ def integrate_bag(args, bag, points_topic, intensity_channel, integrator, warn=_
             raise ValueError(f"error: big-endian point data is not read {where}")
         if cloud.data.size < rosbag1.num_points(cloud) * cloud.point_step:
             raise ValueError(f"error: {cloud.data.size} data bytes for {cloud.width} x {cloud.height} points of {cloud.point_step} bytes {where}")
-        if not keeper.process(*frame_times(cloud, where)):
+        times = frame_times(cloud, where)
+        if timed is None:
+            keep = keeper.process(*times)
+        else:
+            field = time_field(cloud) if times[1] is not None else None
+            keep, scale, shift = keeper.process_times(*times, raw_scale=1e-9 if field is not None and field.datatype == rosbag1.UINT32 else 1.0)
+        if not keep:
             warn("warning: skip frame with an invalid timestamp!!")
             rewound += 1
             continue
         try:
-            nonfinite += integrator.insert_cloud2(cloud, intensity_channel)
+            if timed is None:
+                nonfinite += integrator.insert_cloud2(cloud, intensity_channel)
+            else:
+                nonfinite += timed(cloud, intensity_channel, None if field is None else (field.offset, field.datatype), scale, shift)
         except ValueError as e:
             raise ValueError(f"error: {e} {where}") from None
         inserted += 1
@@ -282,7 +301,8 @@ def main(argv=None):
         parser.print_help()
         return 0
     if args.dynamic_lidar_integration:
-        print("error: dynamic LiDAR integration (-d, CT-GICP) is not built here; only the static integration path is. Run without -d.", file=sys.stderr)
+        print("error: dynamic LiDAR integration (-d, CT-GICP) is a command of its own: python -m direct_visual_lidar_calibration_amd.preprocess_dynamic <bags> <dst> "
+              "takes the same options. This command runs the static integration path only; run it without -d.", file=sys.stderr)
         return 1
     try:
         run(args)

@@ -169,3 +169,180 @@ def delta_trans_rot(a, b):
     d = compose(inverse(a), b)
     ang = 2.0 * np.arctan2(np.linalg.norm(d[:3]), abs(d[3]))
     return float(np.linalg.norm(d[4:])), float(ang)
+
+
+# ---- gtsam Pose3 on 4x4 matrices, xi = [omega; v], right-hand increments (what the CT-GICP factor of the dynamic integrator uses) ----
+def rot3_expmap(omega):
+    """gtsam ``SO3::Expmap`` (Rodrigues; ``I + hat(omega)`` where ``|omega|^2 <= eps``)"""
+    omega = np.asarray(omega, float)
+    theta2 = float(omega @ omega)
+    W = hat(omega)
+    if theta2 <= np.finfo(float).eps:
+        return np.eye(3) + W
+    theta = np.sqrt(theta2)
+    return np.eye(3) + np.sin(theta) / theta * W + (1.0 - np.cos(theta)) / theta2 * (W @ W)
+
+
+def rot3_logmap(R):
+    """gtsam ``SO3::Logmap``: the rotation vector of R, with its branches near 0 and near pi"""
+    tr = float(np.trace(R))
+    if tr + 1.0 < 1e-10:  # angle pi: the axis from the largest diagonal entry
+        i = int(np.argmax(np.diag(R)))
+        e = np.zeros(3)
+        e[i] = 1.0
+        return np.pi / np.sqrt(2.0 + 2.0 * R[i, i]) * (R[:, i] + e)
+    v = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    tr_3 = tr - 3.0
+    if tr_3 < -1e-7:
+        theta = np.arccos(min(1.0, max(-1.0, 0.5 * (tr - 1.0))))
+        magnitude = theta / (2.0 * np.sin(theta))
+    else:  # first-order Taylor around 0
+        magnitude = 0.5 - tr_3 / 12.0
+    return magnitude * v
+
+
+def _series_b_c(theta2):
+    """``(1 - cos theta) / theta^2`` and ``(theta - sin theta) / theta^3`` to theta^6 (exact to rounding for ``theta <= 1e-2``)"""
+    b = 0.5 - theta2 * (1.0 / 24.0 - theta2 * (1.0 / 720.0 - theta2 / 40320.0))
+    c = 1.0 / 6.0 - theta2 * (1.0 / 120.0 - theta2 * (1.0 / 5040.0 - theta2 / 362880.0))
+    return b, c
+
+
+def rot3_expmap_derivative(omega):
+    """Right Jacobian of SO(3): ``Expmap(omega + d) ~ Expmap(omega) Expmap(J d)``"""
+    omega = np.asarray(omega, float)
+    theta2 = float(omega @ omega)
+    W = hat(omega)
+    if theta2 <= 1e-4:  # (the closed forms subtract nearly equal numbers below)
+        b, c = _series_b_c(theta2)
+        return np.eye(3) - b * W + c * (W @ W)
+    theta = np.sqrt(theta2)
+    return np.eye(3) - (1.0 - np.cos(theta)) / theta2 * W + (theta - np.sin(theta)) / (theta2 * theta) * (W @ W)
+
+
+def rot3_logmap_derivative(omega):
+    """Inverse of ``rot3_expmap_derivative``"""
+    omega = np.asarray(omega, float)
+    theta2 = float(omega @ omega)
+    W = hat(omega)
+    if theta2 <= 1e-8:
+        return np.eye(3) + 0.5 * W + (1.0 / 12.0 + theta2 / 720.0) * (W @ W)
+    theta = np.sqrt(theta2)
+    return np.eye(3) + 0.5 * W + (1.0 / theta2 - (1.0 + np.cos(theta)) / (2.0 * theta * np.sin(theta))) * (W @ W)
+
+
+def _pose3_q(xi):
+    """The off-diagonal block of the right Jacobian of SE(3) (Barfoot's Q, eq. 7.86b, at -xi; gtsam ``computeQforExpmapDerivative``);
+    series of the three coefficients below ``|omega| = 1e-2``"""
+    w, v = -np.asarray(xi[:3], float), -np.asarray(xi[3:], float)
+    W, V = hat(w), hat(v)
+    phi2 = float(w @ w)
+    phi = np.sqrt(phi2)
+    if phi < 1e-2:  # (the closed forms subtract nearly equal numbers: b has no correct digit left at phi = 1e-4)
+        p4 = phi2 * phi2
+        a = 1.0 / 6.0 - phi2 / 120.0 + p4 / 5040.0
+        b = -1.0 / 24.0 + phi2 / 720.0 - p4 / 40320.0
+        c = b - 3.0 * (-1.0 / 120.0 + phi2 / 5040.0 - p4 / 362880.0)
+    else:
+        a = (phi - np.sin(phi)) / (phi2 * phi)
+        b = (1.0 - 0.5 * phi2 - np.cos(phi)) / (phi2 * phi2)
+        c = b - 3.0 * (phi - np.sin(phi) - phi2 * phi / 6.0) / (phi2 * phi2 * phi)
+    WV, VW, WVW = W @ V, V @ W, W @ V @ W
+    return 0.5 * V + a * (WV + VW + WVW) - b * (W @ WV + VW @ W - 3.0 * WVW) - 0.5 * c * (WVW @ W + W @ WVW)
+
+
+def pose3_expmap_derivative(xi):
+    """gtsam ``Pose3::ExpmapDerivative`` (6x6): ``Expmap(xi + d) ~ Expmap(xi) Expmap(J d)``"""
+    J = np.zeros((6, 6))
+    Jw = rot3_expmap_derivative(xi[:3])
+    J[:3, :3] = Jw
+    J[3:, 3:] = Jw
+    J[3:, :3] = _pose3_q(xi)
+    return J
+
+
+def pose3_logmap(T):
+    """gtsam ``Pose3::Logmap``: 4x4 -> xi = [omega; v]"""
+    w = rot3_logmap(T[:3, :3])
+    t = np.asarray(T[:3, 3], float)
+    theta = np.linalg.norm(w)
+    if theta < 1e-10:
+        return np.concatenate([w, t])
+    W = hat(w / theta)
+    Wt = W @ t
+    u = t - (0.5 * theta) * Wt + (1.0 - theta / (2.0 * np.tan(0.5 * theta))) * (W @ Wt)
+    return np.concatenate([w, u])
+
+
+def pose3_logmap_derivative(xi):
+    """gtsam ``Pose3::LogmapDerivative`` at xi = Logmap(T): d Logmap(T Expmap(d)) / d d"""
+    J = np.zeros((6, 6))
+    Jw = rot3_logmap_derivative(xi[:3])
+    J[:3, :3] = Jw
+    J[3:, 3:] = Jw
+    J[3:, :3] = -Jw @ _pose3_q(xi) @ Jw
+    return J
+
+
+def pose3_exp(xi):
+    """``Pose3::Expmap`` as ``pose3_expmap`` above, with the series of the translation's coefficients below ``|omega| = 1e-2``
+    (where ``(1 - cos) / theta^2`` has lost half its digits) and gtsam's first-order rotation at ``|omega|^2 <= eps``"""
+    omega, v = np.asarray(xi[:3], float), np.asarray(xi[3:], float)
+    theta2 = float(omega @ omega)
+    W = hat(omega)
+    if theta2 <= 1e-4:
+        b, c = _series_b_c(theta2)
+        V = np.eye(3) + b * W + c * (W @ W)
+    else:
+        theta = np.sqrt(theta2)
+        V = np.eye(3) + (1.0 - np.cos(theta)) / theta2 * W + (theta - np.sin(theta)) / (theta2 * theta) * (W @ W)
+    T = np.eye(4)
+    T[:3, :3] = rot3_expmap(omega)
+    T[:3, 3] = V @ v
+    return T
+
+
+def pose3_expmap_with_derivative(xi):
+    """``(Pose3::Expmap(xi), its 6x6 derivative)``"""
+    return pose3_exp(xi), pose3_expmap_derivative(xi)
+
+
+def pose3_adjoint(T):
+    """``Pose3::AdjointMap`` in [omega; v] order"""
+    R, t = T[:3, :3], T[:3, 3]
+    A = np.zeros((6, 6))
+    A[:3, :3] = R
+    A[3:, 3:] = R
+    A[3:, :3] = hat(t) @ R
+    return A
+
+
+def pose3_inverse(T):
+    Ti = np.eye(4)
+    Ti[:3, :3] = T[:3, :3].T
+    Ti[:3, 3] = -(T[:3, :3].T @ T[:3, 3])
+    return Ti
+
+
+def pose3_between(T1, T2):
+    """``T1.between(T2, H1, H2)`` = ``(T1^-1 T2, -Ad(result^-1), I)``"""
+    D = pose3_inverse(T1) @ T2
+    return D, -pose3_adjoint(pose3_inverse(D)), np.eye(6)
+
+
+def pose3_compose(T1, T2):
+    """``T1.compose(T2, H1, H2)`` = ``(T1 T2, Ad(T2^-1), I)``"""
+    return T1 @ T2, pose3_adjoint(pose3_inverse(T2)), np.eye(6)
+
+
+def pose3_retract(T, xi):
+    """``T * Expmap(xi)``: the increment the optimiser of the dynamic integrator applies"""
+    return T @ pose3_exp(xi)
+
+
+def pose3_interpolate_rt(T0, T1, t):
+    """``Pose3::interpolateRt``: the rotation ``R0 Expmap(t Logmap(R0^T R1))``, the translation interpolated linearly"""
+    T = np.eye(4)
+    T[:3, :3] = T0[:3, :3] @ rot3_expmap(t * rot3_logmap(T0[:3, :3].T @ T1[:3, :3]))
+    T[:3, 3] = T0[:3, 3] + t * (T1[:3, 3] - T0[:3, 3])
+    return T

@@ -41,6 +41,8 @@
  *                            mt19937 streams of src/vlcal/common/estimate_pose.cpp:90-108
  *   nidreg_integrator_*      vlcal::StaticPointCloudIntegrator, insert_points / get_points
  *                            (src/vlcal/preprocess/static_point_cloud_integrator.cpp:25-62)
+ *   nidreg_odom_*            vlcal::DynamicPointCloudIntegrator: kNN covariances, the iVox model, CT-GICP linearise / error, deskewed insert
+ *                            (src/vlcal/preprocess/dynamic_point_cloud_integrator.cpp:50-155)
  *   nidreg_destroy           ~NIDCost / ~CostCalculatorNID
  *
  * Conventions
@@ -83,6 +85,7 @@ extern "C" {
 #define NIDREG_ERR_INVALID (-1)     /* bad argument / unsupported configuration */
 #define NIDREG_ERR_HIP (-2)         /* HIP runtime error */
 #define NIDREG_ERR_NO_DEVICE (-3)   /* no usable gfx950 device */
+#define NIDREG_ERR_FULL (-4)        /* a fixed-size device pool is exhausted (nidreg_odom_model_insert) */
 
 /* camera models (create_camera.cpp:34-51) */
 #define NIDREG_MODEL_PLUMB_BOB 0            /* "plumb_bob": 4 intrinsics, 5 distortion (k1 k2 p1 p2 k3) */
@@ -394,6 +397,63 @@ int nidreg_integrator_size(nidreg_integrator* h, int64_t* num_voxels);
 int nidreg_integrator_get(nidreg_integrator* h, float* records16 /* num_voxels x {x, y, z, intensity} */, int64_t* seq /* optional, may be NULL */);
 int nidreg_integrator_info(nidreg_integrator* h, int64_t* info4);
 void nidreg_integrator_destroy(nidreg_integrator* h);
+
+/* ---- scan-to-model odometry: vlcal::DynamicPointCloudIntegrator (src/vlcal/preprocess/dynamic_point_cloud_integrator.cpp) ------------
+ * The device side of `preprocess -d` (csrc/nid_odom_kernels.hpp); the Levenberg-Marquardt loop over the 12 unknowns runs on the host
+ * (odometry.py).  All arrays are host memory, all arithmetic fp64, no floating-point atomics: every output has the same bits from run
+ * to run.  Points are x y z (3 doubles), covariances xx xy xz yy yz zz (6 doubles).
+ *   nidreg_odom_create        the model: iVox(voxel_resolution, insertion_dist_thresh) (src/vlcal/common/ivox.cpp; the reference uses
+ *                             1.0 and 0.05) -- a hash of voxels under the integrator's packed 64-bit key, each voxel an ordered list of
+ *                             points in chained blocks of 64 from a pool that grows up to max_blocks (1..2^24; 4.6 KB a block).  NOT
+ *                             built: the LRU eviction (lru_thresh); the model only grows.
+ *   nidreg_odom_knn_covariances  for m points the k nearest of each among them (itself included; 2 <= k <= 32 and k <= m, else
+ *                             NIDREG_ERR_INVALID), ordered by ascending (squared distance, index), into neighbors (m x k, nullable);
+ *                             then CloudCovarianceEstimation::estimate(points, neighbors) (cloud_covariance_estimation.cpp:77-112): the
+ *                             neighbour set's covariance (/ (k - 1)), PLANE-regularised: covs = I - 0.999 n n^T with n (normals, m x 3,
+ *                             nullable) the unit eigenvector of its smallest eigenvalue by a closed-form 3x3 solver (sign unspecified).
+ *   nidreg_odom_covariances   the same from a GIVEN neighbour list (the reference reuses the lists on the deskewed points)
+ *   nidreg_odom_model_insert  iVox::insert: points in ascending index; a point enters its voxel iff its squared distance to every point
+ *                             already there is > insertion_dist_thresh^2.  A non-finite point or a voxel index outside [-2^20, 2^20)
+ *                             refuses the call (NIDREG_ERR_INVALID, nothing inserted); an exhausted pool is NIDREG_ERR_FULL (points of
+ *                             this call are then missing from the model: never silently).  A voxel enters the table only with its
+ *                             first block (the table has >= 2 x max_blocks slots, so it stays at most half full), so a dry pool
+ *                             leaves nothing behind and every later call that still needs a block reports NIDREG_ERR_FULL again.
+ *   nidreg_odom_model_info    [0] voxels, [1] points, [2] blocks in use, [3] max_blocks
+ *   nidreg_odom_model_get     every point of the model: voxels in ascending key order, a voxel's points in list order
+ *   nidreg_odom_set_source    the scan's sampled points, their covariances and time-table indices (>= 0), uploaded once per scan
+ *   nidreg_odom_linearize     IntegratedCT_GICPFactor_::linearize (include/vlcal/common/integrated_ct_gicp_factor_impl.hpp:70-177).  poses:
+ *                             per time-table entry 84 doubles -- the pose (R row-major 9, t 3) and its 6 x 6 derivatives by pose 0 and by
+ *                             pose 1 (row-major, gtsam's [omega, v] order).  Per source point: the nearest model point over the 7
+ *                             face-neighbour voxels of the transformed point (a tie goes to the later one, as in the reference), rejected
+ *                             when none or further than max_correspondence_dist_sq; (C_B + R C_A R^T)^-1; the terms of out122 = H_00 (36,
+ *                             row-major) H_01 (36) H_11 (36) b_0 (6) b_1 (6) error count.  (gtsam's HessianFactor takes -b.)  Per-wave
+ *                             partials summed in wave order.  Correspondences and Mahalanobis matrices are kept.
+ *   nidreg_odom_error         ::error (:40-67) at other poses (12 doubles per entry) on the kept correspondences: out2 = error, count
+ *   nidreg_odom_correspondences  per source point: found (0 / 1), the matched model point (3), the Mahalanobis matrix (9); nullable
+ *   nidreg_odom_deskew_insert voxelgrid_task (:123-155) for one raw PointCloud2 frame into a voxel integrator: the arguments of
+ *                             nidreg_integrator_insert_cloud2, the time field (time_datatype UINT32 (6), FLOAT32 (7) or FLOAT64 (8): time =
+ *                             value * time_scale + time_shift [s]; 0 = no field: time = time_scale * index / num_points), max_time (<= 0:
+ *                             every point at t = 0), and the motion: begin12 = T_begin (R row-major, t), rotvec3 = Logmap(R_begin^T
+ *                             R_end), dtrans3 = t_end - t_begin.  Per point t = time / max_time, the pose interpolateRt(T_begin, T_end, t),
+ *                             the transformed point; then the integrator's own passes: non-finite points skipped and counted,
+ *                             |p| < min_distance in the odometry frame skipped, sequence number = offered + index in the message.
+ *                             Two differences from the reference: it refreshes the pose only every 1e-4 of normalised time along the
+ *                             time-sorted order, and within a frame its latest-in-time point of a voxel wins (here: the highest index). */
+typedef struct nidreg_odom nidreg_odom;
+int nidreg_odom_create(int device_id, double voxel_resolution, double insertion_dist_thresh, int32_t max_blocks, nidreg_odom** out);
+void nidreg_odom_destroy(nidreg_odom* h);
+int nidreg_odom_knn_covariances(nidreg_odom* h, const double* points, int32_t m, int32_t k, int32_t* neighbors, double* normals, double* covs);
+int nidreg_odom_covariances(nidreg_odom* h, const double* points, int32_t m, int32_t k, const int32_t* neighbors, double* normals, double* covs);
+int nidreg_odom_model_insert(nidreg_odom* h, const double* points, const double* covs, int32_t m);
+int nidreg_odom_model_info(nidreg_odom* h, int64_t* info4);
+int nidreg_odom_model_get(nidreg_odom* h, int32_t* voxels /* points x 3 */, double* points /* points x 3 */, double* covs /* points x 6, nullable */);
+int nidreg_odom_set_source(nidreg_odom* h, const double* points, const double* covs, const int32_t* time_index, int32_t m);
+int nidreg_odom_linearize(nidreg_odom* h, const double* poses /* num_poses x 84 */, int32_t num_poses, double max_correspondence_dist_sq, double* out122);
+int nidreg_odom_error(nidreg_odom* h, const double* poses12 /* num_poses x 12 */, int32_t num_poses, double* out2);
+int nidreg_odom_correspondences(nidreg_odom* h, int32_t* found, double* target, double* mahalanobis);
+int nidreg_odom_deskew_insert(nidreg_integrator* integrator, const void* data, int64_t num_points, int32_t point_step, int32_t x_offset, int32_t y_offset, int32_t z_offset, int32_t xyz_datatype,
+                              int32_t intensity_offset, int32_t intensity_datatype, int32_t time_offset, int32_t time_datatype, double time_scale, double time_shift, double max_time,
+                              const double* begin12, const double* rotvec3, const double* dtrans3, int64_t* num_skipped);
 
 /* ---- split-phase evaluation for a pair whose points are sharded across GPUs --------------
  * rank r:  nidreg_shard_hist(h, se3)      zero + accumulate this shard's fixed-point histogram
