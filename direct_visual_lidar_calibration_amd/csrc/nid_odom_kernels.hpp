@@ -7,7 +7,9 @@
 //                        covariance of a neighbour list (divided by k - 1) and its PLANE regularisation (:133-148).
 //                        V diag(1e-3, 1, 1) V^-1 = I - 0.999 n n^T with n the eigenvector of the smallest eigenvalue, so only n
 //                        is computed: the closed-form symmetric 3x3 solver of Eigen's computeDirect (shift by the mean eigenvalue,
-//                        scale by the largest coefficient, trigonometric roots, cross products for the kernel of A - lambda I).
+//                        scale by the largest coefficient, trigonometric roots, cross products for the kernel of A - lambda I of
+//                        the better separated end); where that end is the largest eigenvalue, n comes from the 2 x 2 problem in
+//                        its eigenvector's orthogonal complement.
 //   k_odom_model_insert  iVox::insert (ivox.cpp:122-166) without the LRU eviction: a hash of 1 m voxels (the integrator's packed
 //                        64-bit key), each voxel an ordered list of points with their covariances in chained blocks of 64 from a
 //                        pool.  LinearContainer::insert's rule (:29-50) is sequential -- a point enters iff its squared distance to
@@ -155,19 +157,35 @@ __device__ inline void odom_smallest_eigvec(double a00, double a10, double a11, 
     if (odom_kernel_vec(m00 - l0, m10, m11 - l0, m20, m21, m22 - l0, v)) n[0] = v[0], n[1] = v[1], n[2] = v[2];
     return;
   }
-  if (d_lo > 2.0 * eps * d_hi && odom_kernel_vec(m00 - l0, m10, m11 - l0, m20, m21, m22 - l0, v)) {
-    n[0] = v[0], n[1] = v[1], n[2] = v[2];
-    return;
-  }
-  // the two small eigenvalues coincide numerically (a line of points): any unit vector orthogonal to the largest one's eigenvector
+  // The LARGEST eigenvalue is the better separated end.  The trigonometric roots lose digits where two of them are close (q above is a
+  // difference of nearly equal numbers): l0 and l1 move with theta to first order, l2 only to second.  The kernel of A - l0 I then
+  // carries an error of (error of l0) / (l1 - l0), 2e-6 for a strip of points 1000 times longer than wide, where LAPACK's
+  // iteration has 1e-10.  So the well-separated eigenvector comes first, and the smallest one from the 2 x 2 problem in its
+  // orthogonal complement, whose closed form has no such cancellation.
   if (!odom_kernel_vec(m00 - l2, m10, m11 - l2, m20, m21, m22 - l2, v)) return;
-  if (fabs(v[0]) > fabs(v[2]) || fabs(v[1]) > fabs(v[2])) {  // Eigen's unitOrthogonal
+  double u[3];  // Eigen's unitOrthogonal of v, then w = v x u
+  if (fabs(v[0]) > fabs(v[2]) || fabs(v[1]) > fabs(v[2])) {
     const double s = sqrt(v[0] * v[0] + v[1] * v[1]);
-    n[0] = -v[1] / s, n[1] = v[0] / s, n[2] = 0.0;
+    u[0] = -v[1] / s, u[1] = v[0] / s, u[2] = 0.0;
   } else {
     const double s = sqrt(v[1] * v[1] + v[2] * v[2]);
-    n[0] = 0.0, n[1] = -v[2] / s, n[2] = v[1] / s;
+    u[0] = 0.0, u[1] = -v[2] / s, u[2] = v[1] / s;
   }
+  const double w[3] = {v[1] * u[2] - v[2] * u[1], v[2] * u[0] - v[0] * u[2], v[0] * u[1] - v[1] * u[0]};
+  const double mu[3] = {(m00 * u[0] + m10 * u[1]) + m20 * u[2], (m10 * u[0] + m11 * u[1]) + m21 * u[2], (m20 * u[0] + m21 * u[1]) + m22 * u[2]};
+  const double mw[3] = {(m00 * w[0] + m10 * w[1]) + m20 * w[2], (m10 * w[0] + m11 * w[1]) + m21 * w[2], (m20 * w[0] + m21 * w[1]) + m22 * w[2]};
+  // [a b; b c] = [u w]^T A [u w]; its smaller eigenvalue is (a + c) / 2 - r, the eigenvector (b, -h - r) or (h - r, b): the one whose
+  // difference adds magnitudes
+  const double a = (u[0] * mu[0] + u[1] * mu[1]) + u[2] * mu[2], b = (u[0] * mw[0] + u[1] * mw[1]) + u[2] * mw[2], c = (w[0] * mw[0] + w[1] * mw[1]) + w[2] * mw[2];
+  const double h = 0.5 * (a - c), r = sqrt(h * h + b * b);
+  double x = h >= 0.0 ? b : h - r, y = h >= 0.0 ? -h - r : b;
+  const double s = sqrt(x * x + y * y);
+  if (!(s > 0.0) || !isfinite(s)) {  // the two small eigenvalues coincide (a line of points): any unit vector orthogonal to v
+    n[0] = u[0], n[1] = u[1], n[2] = u[2];
+    return;
+  }
+  x /= s, y /= s;
+  n[0] = x * u[0] + y * w[0], n[1] = x * u[1] + y * w[1], n[2] = x * u[2] + y * w[2];
 }
 
 __global__ __launch_bounds__(kOdomWave) void k_odom_cov(const double* pts, const int* nbr, int M, int k, double* normals /* M x 3 */, double* covs /* M x 6 */) {

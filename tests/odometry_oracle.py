@@ -3,7 +3,7 @@ sources: src/vlcal/preprocess/dynamic_point_cloud_integrator.cpp, src/vlcal/comm
 include/vlcal/common/integrated_ct_icp_factor_impl.hpp, include/vlcal/common/integrated_ct_gicp_factor_impl.hpp,
 src/vlcal/common/cloud_covariance_estimation.cpp, src/vlcal/common/frame_cpu.cpp and src/vlcal/common/time_keeper.cpp.
 
-It is the yardstick of tests/test_odometry_gpu.py, together with a synthetic ground truth.  The reference's own integrator cannot be
+It is the yardstick of tests/test_odometry_gpu.py and tests/test_odometry_edges.py, together with a synthetic ground truth.  The reference's own integrator cannot be
 compiled for these tests: it needs gtsam, PCL and ROS, none of which is available.  So the optimiser is the project's own
 (``odometry.levenberg_marquardt`` through ``odometry.ScanMatcher``, unpinned against gtsam); what this module replaces is everything the
 GPU does: ``NumpyBackend`` has ``odometry.DeviceBackend``'s methods.
@@ -27,8 +27,9 @@ def sq_dists(points, q):
 
 
 def knn(points, k):
-    """``(neighbors (m, k), distances (m, k + 1))``: ascending (d^2, index); the extra distance column (inf when m == k) lets a
-    test see that no tie decides a set.  Brute force, 1024 queries at a time."""
+    """``(neighbors (m, k), distances (m, k + 1))``: ascending (d^2, index) over ALL candidates, so a tie -- inside a list or at
+    the k / k + 1 boundary -- goes to the lower index, as k_odom_knn's insertion does; the extra distance column (inf when m == k)
+    lets a test see whether a tie decides a set.  Brute force: a stable sort of every full row, 1024 queries at a time."""
     m = points.shape[0]
     keep = min(k + 1, m)
     nbr, dist = np.empty((m, k), dtype=np.int32), np.full((m, k + 1), np.inf)
@@ -36,11 +37,9 @@ def knn(points, k):
         d = points[r0 : r0 + 1024, None, :] - points[None, :, :]
         d = (d[:, :, 0] * d[:, :, 0] + d[:, :, 1] * d[:, :, 1]) + d[:, :, 2] * d[:, :, 2]
         rows = d.shape[0]
-        cand = np.sort(np.argpartition(d, keep - 1, axis=1)[:, :keep], axis=1) if keep < m else np.tile(np.arange(m), (rows, 1))
-        dc = np.take_along_axis(d, cand, axis=1)
-        by_dist = np.argsort(dc, axis=1, kind="stable")  # (stable over ascending indices: equal distances stay in index order)
-        nbr[r0 : r0 + rows] = np.take_along_axis(cand, by_dist, axis=1)[:, :k]
-        dist[r0 : r0 + rows, :keep] = np.take_along_axis(dc, by_dist, axis=1)
+        order = np.argsort(d, axis=1, kind="stable")[:, :keep]  # (stable over ascending indices: equal distances stay in index order)
+        nbr[r0 : r0 + rows] = order[:, :k]
+        dist[r0 : r0 + rows, :keep] = np.take_along_axis(d, order, axis=1)
     return nbr, dist
 
 
@@ -98,14 +97,23 @@ class IVox:
         return self._flat
 
     def nearest(self, q):
-        """iVox::nearest_neighbor_search (:207-245) for all rows of q: ``(index into flat() or -1, d^2)``; a tie goes to the later"""
+        """iVox::nearest_neighbor_search (:207-245) for all rows of q: ``(index into flat() or -1, d^2)``; a tie goes to the later.
+        As odom_nearest does, a neighbour voxel outside [-2^20, 2^20) on an axis is skipped (the model holds no such voxel, and
+        ``pack_key`` never sees its index), and a non-finite row finds nothing."""
         keys, pts, _ = self.flat()
         n = q.shape[0]
         best, index = np.full(n, DBL_MAX), np.full(n, -1, dtype=np.int64)
-        centre = np.floor(q / self.res).astype(np.int64)
+        with np.errstate(invalid="ignore"):
+            fc = np.floor(q / self.res)
+        sane = np.all(np.isfinite(fc) & (fc >= -AXIS_LIMIT - 1) & (fc <= AXIS_LIMIT), axis=1)
+        centre = np.where(sane[:, None], fc, 0.0).astype(np.int64)
         for off in OFFSETS:
-            k = pack_key((centre[:, 0] + off[0], centre[:, 1] + off[1], centre[:, 2] + off[2]))
+            v = centre + np.asarray(off, dtype=np.int64)[None]
+            inside = sane & np.all((v >= -AXIS_LIMIT) & (v < AXIS_LIMIT), axis=1)
+            v = np.where(inside[:, None], v, 0)
+            k = pack_key((v[:, 0], v[:, 1], v[:, 2]))
             lo, hi = np.searchsorted(keys, k, side="left"), np.searchsorted(keys, k, side="right")
+            hi = np.where(inside, hi, lo)
             for j in range(int((hi - lo).max()) if n else 0):
                 rows = np.flatnonzero(lo + j < hi)
                 cand = lo[rows] + j
@@ -116,8 +124,25 @@ class IVox:
         return index, best
 
 
+AXIS_LIMIT = 1 << 20  # kVoxAxisLimit: a voxel index lies in [-2^20, 2^20) on every axis
+_U64 = (1 << 64) - 1
+
+
 def pack_key(v):
     return (np.asarray(v[0], dtype=np.int64) + (1 << 20)) | ((np.asarray(v[1], dtype=np.int64) + (1 << 20)) << 21) | ((np.asarray(v[2], dtype=np.int64) + (1 << 20)) << 42)
+
+
+def vox_mix(z):
+    """``vox_mix`` of csrc/nid_voxel_kernels.hpp (splitmix64's finaliser) on a Python int, masked to 64 bits"""
+    z &= _U64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _U64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _U64
+    return z ^ (z >> 31)
+
+
+def home_slot(voxel, mask):
+    """Where the probe for ``voxel`` (three ints) starts in a table of ``mask + 1`` slots: the table's key is the packed voxel + 1"""
+    return vox_mix(int(pack_key(tuple(int(c) for c in voxel))) + 1) & 0xFFFFFFFF & mask
 
 
 # ---- CT-GICP ------------------------------------------------------------------------------------------------------------------------

@@ -225,3 +225,73 @@ def test_preprocess_ros1_still_refuses_dynamic_integration(tmp_path, capsys):
     assert preprocess_ros1.main([str(tmp_path), str(tmp_path / "out"), "-d"]) == 1
     err = capsys.readouterr().err
     assert "dynamic LiDAR integration" in err and "preprocess_dynamic" in err and not (tmp_path / "out").exists()
+
+
+# ---- the oracle's own pins (tests/odometry_oracle.py is the yardstick of the GPU tests) ----------------------------------------------
+def test_oracle_knn_orders_by_distance_then_index_under_ties():
+    """A shuffled 5 x 5 x 3 integer lattice, k = 8: exact distances, so ties are true ties, at the k / k + 1 boundary too; a partition
+    before the sort (the earlier oracle) kept an arbitrary subset of a tied boundary group and differed here in 35 of 75 rows"""
+    g = np.stack(np.meshgrid(np.arange(5), np.arange(5), np.arange(3), indexing="ij"), axis=-1).reshape(-1, 3).astype(np.float64)
+    pts = g[np.random.default_rng(0).permutation(75)]
+    nbr, dist = oracle.knn(pts, 8)
+    assert nbr.shape == (75, 8) and nbr.dtype == np.int32 and dist.shape == (75, 9)
+    tied = 0
+    for i in range(75):
+        d = [float(np.sum((pts[j] - pts[i]) ** 2)) for j in range(75)]
+        order = sorted(range(75), key=lambda j: (d[j], j))
+        assert nbr[i].tolist() == order[:8] and dist[i].tolist() == [d[j] for j in order[:9]]
+        tied += d[order[7]] == d[order[8]]
+    assert tied >= 19  # a tie decides the set in a quarter of the rows at least
+    nbr, dist = oracle.knn(pts[:8], 8)  # m == k: everything, and no next distance
+    assert np.array_equal(np.sort(nbr, axis=1), np.tile(np.arange(8), (8, 1))) and np.all(np.isinf(dist[:, 8]))
+
+
+def test_oracle_hash_is_splitmix64_and_home_slot_takes_the_packed_key_plus_one():
+    assert oracle.vox_mix(0x9E3779B97F4A7C15) == 0xE220A8397B1DCDAF  # splitmix64's first output from seed 0
+    assert oracle.vox_mix(0) == 0 and oracle.vox_mix((1 << 64) + 5) == oracle.vox_mix(5)
+    key = int(oracle.pack_key((3, -2, 7))) + 1
+    assert key == ((3 + (1 << 20)) | ((-2 + (1 << 20)) << 21) | ((7 + (1 << 20)) << 42)) + 1
+    assert oracle.home_slot((3, -2, 7), 1023) == oracle.vox_mix(key) & 1023 and oracle.home_slot((3, -2, 7), (1 << 25) - 1) == oracle.vox_mix(key) & ((1 << 25) - 1)
+    homes = [oracle.home_slot(v, 1023) for v in np.ndindex(12, 12, 12)]
+    assert min(homes) >= 0 and max(homes) <= 1023 and len(set(homes)) > 800  # spread over the table
+
+
+def test_oracle_nearest_honours_the_resolution_and_never_packs_a_voxel_outside_the_key_range(monkeypatch):
+    top = 2.0**20
+    packed = []
+    real = oracle.pack_key
+    monkeypatch.setattr(oracle, "pack_key", lambda v: packed.append(np.stack([np.asarray(c, dtype=np.int64) for c in v])) or real(v))
+    for res in (1.0, 0.5, 0.3):
+        ivox = oracle.IVox(resolution=res, insertion_dist_thresh=0.01)
+        model = np.array([[top - 0.25, 0.5, 0.5], [-top + 0.25, 0.5, 0.5], [0.5, 0.5, 0.5], [1.25, 2.5, 0.5]]) * res
+        ivox.insert(model, np.ones((4, 6)))
+        assert sorted(ivox.voxels) == sorted([(2**20 - 1, 0, 0), (-(2**20), 0, 0), (0, 0, 0), (1, 2, 0)])  # floor(p / res)
+        q = np.array([[top - 0.75, 0.5, 0.5], [top + 0.5, 0.5, 0.5], [top + 1.5, 0.5, 0.5], [-top - 0.5, 0.5, 0.5], [-top - 1.5, 0.5, 0.5], [np.nan, 0.5, 0.5], [0.5, np.inf, 0.5],
+                      [0.75, 2.5, 0.5], [1.25, 3.5, 0.5], [0.75, 3.5, 0.5]]) * res  # the last three: the -x face neighbour, the -y one, an edge-diagonal voxel
+        index, dist = ivox.nearest(q)
+        _, pts, _ = ivox.flat()
+        assert (index >= 0).tolist() == [True, True, False, True, False, False, False, True, True, False]
+        assert np.array_equal(pts[index[[0, 1, 3, 7, 8]]], model[[0, 0, 1, 3, 3]])
+        assert np.allclose(dist[[0, 1, 3]], np.array([0.25, 0.5625, 0.5625]) * res * res, rtol=1e-9, atol=0.0) and np.all(dist[index < 0] == oracle.DBL_MAX)
+    every = np.concatenate([p.reshape(3, -1) for p in packed], axis=1)
+    assert every.min() >= -(2**20) and every.max() < 2**20
+
+
+def test_the_eigen_fixture_regenerates_identically():
+    import make_odometry_golden as golden
+
+    stored = np.load(golden.PATH)
+    assert os.path.getsize(golden.PATH) < 64 * 1024 and stored["k"].max() <= golden.MAX_POINTS and 24 <= stored["names"].shape[0] <= 48
+    cases = golden.build_cases()  # the inputs need numpy only: always compared
+    assert [c[0] for c in cases] == stored["names"].tolist() and [c[1] for c in cases] == stored["groups"].tolist()
+    for i, (_, _, pts, lst) in enumerate(cases):
+        k = pts.shape[0]
+        assert np.array_equal(stored["points"][i, :k], pts) and np.array_equal(stored["lists"][i, :k], lst) and stored["k"][i] == k
+    try:
+        import mpmath  # noqa: F401
+    except ImportError:
+        pytest.skip("mpmath is not installed: the exact normals of tests/golden/odometry_eigen_cases.npz are not regenerated here")
+    fresh = golden.generate()
+    assert sorted(fresh) == sorted(stored.files)
+    for name in stored.files:
+        assert np.array_equal(fresh[name], stored[name]), name
