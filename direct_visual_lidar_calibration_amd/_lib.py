@@ -16,6 +16,7 @@ NIDREG_FALSE = 1
 NIDREG_ERR_INVALID = -1
 NIDREG_ERR_FULL = -4
 NIDREG_OUT_DOUBLES = 16
+FEATURES_CAPACITY = 65536  # NIDREG_FEATURES_CAPACITY
 
 MODE_SPLINE, MODE_NEAREST = 0, 1
 PREC_FP64 = 0  # (1 = NIDREG_PREC_FP32: removed in round 5, refused by nidreg_create)
@@ -75,6 +76,7 @@ EXPORTS = [
     "nidreg_integrator_destroy",
     "nidreg_odom_create", "nidreg_odom_destroy", "nidreg_odom_knn_covariances", "nidreg_odom_covariances", "nidreg_odom_model_insert", "nidreg_odom_model_info", "nidreg_odom_model_get",
     "nidreg_odom_set_source", "nidreg_odom_linearize", "nidreg_odom_error", "nidreg_odom_correspondences", "nidreg_odom_deskew_insert",
+    "nidreg_features_detect", "nidreg_features_match",
 ]
 
 _lib = None
@@ -168,6 +170,9 @@ def load():
     lib.nidreg_odom_error.argtypes = [ctypes.c_void_p, c_double_p, ctypes.c_int32, c_double_p]
     lib.nidreg_odom_correspondences.argtypes = [ctypes.c_void_p, c_int32_p, c_double_p, c_double_p]
     lib.nidreg_odom_deskew_insert.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_int32] * 9 + [ctypes.c_double] * 3 + [c_double_p] * 3 + [c_int64_p]
+    c_uint8_p, c_uint32_p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32)
+    lib.nidreg_features_detect.argtypes = [ctypes.c_int, c_uint8_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_uint8_p, ctypes.c_int64] + [ctypes.c_int] * 5 + [c_int32_p, c_uint32_p, c_int32_p]
+    lib.nidreg_features_match.argtypes = [ctypes.c_int, c_uint32_p, ctypes.c_int, c_uint32_p, ctypes.c_int] + [ctypes.c_int] * 3 + [c_int32_p] * 3
     lib.nidreg_rccl_unique_id.argtypes = [ctypes.c_char_p]
     lib.nidreg_shard_comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]
     lib.nidreg_shard_attach_rccl.argtypes = [ctypes.c_void_p, ctypes.c_void_p]

@@ -9,7 +9,8 @@ Mirrors the reference executable (src/initial_guess_auto.cpp:26-185):
         [--ransac_error_thresh 10.0] [--robust_kernel_width 10.0] [--seed 0]
 
 Same option names, defaults (:161-165) and ``calib.json`` key; ``--seed`` is an extension (the reference's sampling depends on
-its thread count).  Producing the matches (SuperGlue, find_matches_superglue.py) is not part of this package.
+its thread count).  The matches come from ``find_matches`` (find_matches.py: a FAST / BRIEF stand-in for the reference's SuperGlue script,
+find_matches_superglue.py, whose file this reads just as well).
 """
 import argparse
 import sys

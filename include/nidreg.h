@@ -455,6 +455,48 @@ int nidreg_odom_deskew_insert(nidreg_integrator* integrator, const void* data, i
                               int32_t intensity_offset, int32_t intensity_datatype, int32_t time_offset, int32_t time_datatype, double time_scale, double time_shift, double max_time,
                               const double* begin12, const double* rotvec3, const double* dtrans3, int64_t* num_skipped);
 
+/* ---- find_matches: keypoints and 2D-2D matches between the camera image and the LiDAR intensity image -------------------------------
+ * What initial_guess_auto reads (<bag>_matches.json) the reference produces with scripts/find_matches_superglue.py (SuperGlue: learned
+ * weights under a non-commercial licence, OpenCV).  This is a classical, licence-free STAND-IN, not a port: FAST-9 corners over an
+ * image pyramid, upright BRIEF-256 descriptors, mutual-best Hamming matching with a ratio test (csrc/nid_match_kernels.hpp).  Of the
+ * reference script only the command line and the JSON keys are kept (find_matches.py).  Its quality on real camera / LiDAR pairs is
+ * UNMEASURED.  All arithmetic is integer on 8-bit pixels and no kernel uses an atomic: the outputs equal tests/matching_oracle.py bit
+ * for bit and are the same bytes from run to run.  All arrays are host memory.
+ *   nidreg_features_detect    image: height rows of width 8-bit pixels, row_stride bytes apart.
+ *                             mask (nullable; non-zero = valid, mask_row_stride bytes a row): fill_passes passes first replace every
+ *                             invalid pixel that has a valid 3x3 neighbour by the mean of its valid neighbours, rounded half up, and
+ *                             mark it valid (each pass reads the previous pass's result only); a keypoint is reported only when its
+ *                             level-0 pixel is valid in the mask AS GIVEN (it still suppresses its neighbours).
+ *                             Pyramid: level l + 1 = bilinear from level l at ratio 6/5 -- destination x at source (12 x + 1) / 10, weights
+ *                             in tenths, (sum + 50) / 100, taps clamped --, size floor(5 size / 6); a level with a side <= 32 and all
+ *                             above it hold no keypoint and are not built.  Descriptors read a smoothed copy of the level: the separable
+ *                             binomial [1 4 6 4 1] along x and y (the 5 x 5 kernel of weight 256) rounded once, (sum + 128) >> 8, borders
+ *                             replicated.  Detector (on the unsmoothed level): a pixel is a corner at threshold t when 9 contiguous
+ *                             pixels of the 16-pixel radius-3 circle are all >= centre + t or all <= centre - t; its score is the largest
+ *                             such t (0: none); pixels closer than 16 to the level's edge score 0.  A pixel with score >= fast_threshold
+ *                             survives when no pixel of its (2 nms_radius + 1)^2 window scores higher and no earlier one in (y, x) order
+ *                             scores the same.  Survivors are ordered by (score descending, level, y, x) with a radix sort of one 64-bit
+ *                             key each; the first max_keypoints are kept (-1: all, capped at NIDREG_FEATURES_CAPACITY; the output arrays
+ *                             must hold that many).  kpts_out: n x {x0, y0, level, score}, x0 = ((2 x + 1) 6^l) / (2 5^l) in integer
+ *                             division clamped to the image (y0 alike); desc_out: n x 8 words, bit k of word k / 32 set when the first
+ *                             sample of BRIEF pair k (csrc/nid_brief_table.hpp, offsets in [-15, 15]^2 around the keypoint on the smoothed
+ *                             level) is less than the second.  No orientation: in-plane rotation is the caller's (find_matches
+ *                             --rotate_camera / --rotate_lidar).  *count_out = n.
+ *   nidreg_features_match     per row descriptor of desc0 the best and second-best Hamming distance over desc1 (a tie goes to the lowest
+ *                             column; one column: second = 257), the same with the sides swapped, then match01_out[i] = j when j is i's
+ *                             best, i is j's best, d1 <= max_distance and d1 ratio_den < d2 ratio_num; else -1.  dist_out[i] = d1 whether
+ *                             accepted or not, second_out (nullable) = d2.  n0 == 0 or n1 == 0 is valid: no match (distances 257), no
+ *                             launch.
+ * NIDREG_ERR_INVALID before any device call: a NULL array, a non-positive size (or one above 32768), a stride below the width,
+ * levels outside [1, 16], fast_threshold outside [1, 255], nms_radius outside [0, 16], fill_passes outside [0, 64], max_keypoints 0
+ * or above the capacity, ratio_den <= 0, ratio_num < 0, max_distance < 0, a negative descriptor count. */
+#define NIDREG_FEATURES_CAPACITY 65536
+int nidreg_features_detect(int device_id, const uint8_t* image, int width, int height, int64_t row_stride, const uint8_t* mask /* nullable */, int64_t mask_row_stride, int levels,
+                           int fast_threshold, int nms_radius, int fill_passes, int max_keypoints, int32_t* kpts_out /* n x 4: x0 y0 level score */, uint32_t* desc_out /* n x 8 */,
+                           int32_t* count_out);
+int nidreg_features_match(int device_id, const uint32_t* desc0, int n0, const uint32_t* desc1, int n1, int max_distance, int ratio_num, int ratio_den,
+                          int32_t* match01_out /* n0: column or -1 */, int32_t* dist_out /* n0: best distance */, int32_t* second_out /* n0, nullable */);
+
 /* ---- split-phase evaluation for a pair whose points are sharded across GPUs --------------
  * rank r:  nidreg_shard_hist(h, se3)      zero + accumulate this shard's fixed-point histogram
  *          <caller: all-reduce(sum, int64) of ext_hist over ranks, ordered on ext_stream>
