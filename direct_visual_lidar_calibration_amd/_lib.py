@@ -74,7 +74,7 @@ EXPORTS = [
     "nidreg_estimate_directions", "nidreg_ransac_sample_pairs", "nidreg_estimate_rotation_ransac",
     "nidreg_integrator_create", "nidreg_integrator_insert", "nidreg_integrator_insert_f32", "nidreg_integrator_insert_cloud2", "nidreg_integrator_size", "nidreg_integrator_get", "nidreg_integrator_info",
     "nidreg_integrator_destroy",
-    "nidreg_odom_create", "nidreg_odom_destroy", "nidreg_odom_knn_covariances", "nidreg_odom_covariances", "nidreg_odom_model_insert", "nidreg_odom_model_info", "nidreg_odom_model_get",
+    "nidreg_odom_create", "nidreg_odom_destroy", "nidreg_odom_knn_covariances", "nidreg_odom_covariances", "nidreg_odom_model_insert", "nidreg_odom_model_info", "nidreg_odom_model_get", "nidreg_odom_set_lru", "nidreg_odom_lru_info",
     "nidreg_odom_set_source", "nidreg_odom_linearize", "nidreg_odom_error", "nidreg_odom_correspondences", "nidreg_odom_deskew_insert",
     "nidreg_features_detect", "nidreg_features_match",
 ]
@@ -164,6 +164,8 @@ def load():
     lib.nidreg_odom_covariances.argtypes = [ctypes.c_void_p, c_double_p, ctypes.c_int32, ctypes.c_int32, c_int32_p, c_double_p, c_double_p]
     lib.nidreg_odom_model_insert.argtypes = [ctypes.c_void_p, c_double_p, c_double_p, ctypes.c_int32]
     lib.nidreg_odom_model_info.argtypes = [ctypes.c_void_p, c_int64_p]
+    lib.nidreg_odom_set_lru.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]
+    lib.nidreg_odom_lru_info.argtypes = [ctypes.c_void_p, c_int64_p]
     lib.nidreg_odom_model_get.argtypes = [ctypes.c_void_p, c_int32_p, c_double_p, c_double_p]
     lib.nidreg_odom_set_source.argtypes = [ctypes.c_void_p, c_double_p, c_double_p, c_int32_p, ctypes.c_int32]
     lib.nidreg_odom_linearize.argtypes = [ctypes.c_void_p, c_double_p, ctypes.c_int32, ctypes.c_double, c_double_p]

@@ -10,15 +10,25 @@
 //                        scale by the largest coefficient, trigonometric roots, cross products for the kernel of A - lambda I of
 //                        the better separated end); where that end is the largest eigenvalue, n comes from the 2 x 2 problem in
 //                        its eigenvector's orthogonal complement.
-//   k_odom_model_insert  iVox::insert (ivox.cpp:122-166) without the LRU eviction: a hash of 1 m voxels (the integrator's packed
+//   k_odom_model_insert  iVox::insert (ivox.cpp:122-166): a hash of 1 m voxels (the integrator's packed
 //                        64-bit key), each voxel an ordered list of points with their covariances in chained blocks of 64 from a
 //                        pool.  LinearContainer::insert's rule (:29-50) is sequential -- a point enters iff its squared distance to
 //                        EVERY point already in its voxel is > thresh --, so the scan's points arrive grouped by voxel (ascending
 //                        index inside a group) and ONE wave walks one group in order, its lanes testing a candidate against a block.
+//                        Every voxel a scan offers a point to is stamped with the insert's count (:164), a refused point included.
+//   k_odom_evict         the LRU pass of iVox::insert (:168-178): every voxel whose stamp lies below the horizon leaves.  The table
+//                        is open addressing with linear probing, so nothing is erased in place: one thread per old slot moves a
+//                        survivor (head, tail, count and stamp kept) into a second, zeroed table of the same size, or walks a
+//                        leaving voxel's chain and pushes its blocks onto the free stack odom_alloc_block pops from; the host
+//                        then swaps the two tables.  No tombstones, and the new table holds no more voxels than the old one, so
+//                        odom_find's invariant holds after every pass.  Which slot or block id a voxel gets may differ from run
+//                        to run, as before; no result depends on either.  NOT built: the "too many voxels" branch (:181-197),
+//                        which takes 2^32 - 1 voxels and cannot be reached with a table of at most 2^25 slots.
 //   k_odom_linearize     IntegratedCT_GICPFactor_::update_correspondences + linearize (integrated_ct_gicp_factor_impl.hpp:70-177):
 //                        per source point the pose of its time index, the nearest model point over the 7 face-neighbour voxels
 //                        (iVox::nearest_neighbor_search, ivox.cpp:207-245), the Mahalanobis matrix, and the point's terms of H_00,
-//                        H_01, H_11, b_0, b_1, the error and the inlier count.
+//                        H_01, H_11, b_0, b_1, the error and the inlier count.  With the eviction on (the Touch instantiation) every
+//                        neighbour voxel the search finds in the table is stamped with the current count (:223).
 //   k_odom_error         ::error (:40-67) on the stored correspondences and Mahalanobis matrices at other poses.
 //   k_odom_sum           the per-wave partials of the two kernels above, summed in wave order.
 //   k_odom_deskew        voxelgrid_task (dynamic_point_cloud_integrator.cpp:123-155) up to the voxel insert: the raw
@@ -48,7 +58,7 @@ struct OdomVoxel {
   vox_u64 key;  // packed voxel + 1; 0 = empty
   int head, tail;  // first and last block of the chain
   int count;       // points in the voxel
-  int pad;
+  int last_lru_count;  // the count of the last insert that offered it a point, or after which a search found it (ivox.cpp:164, :223)
 };
 
 // the integrator's packed key of floor(p / res); false outside [-2^20, 2^20) on an axis or for a non-finite coordinate
@@ -212,8 +222,21 @@ __global__ __launch_bounds__(kOdomWave) void k_odom_cov(const double* pts, const
 }
 
 // ---- the model --------------------------------------------------------------------------------------------------------------------
-// counters: [0] blocks handed out, [1] voxels, [2] points, [3] set when the pool ran dry
-__device__ inline int odom_alloc_block(int* next, int cap_blocks, vox_u64* counters) {
+// counters: [0] blocks handed out by the bump counter (the pool's high-water mark), [1] voxels, [2] points, [3] set when the pool ran
+// dry, [4] blocks on the free stack, [5] voxels evicted so far.  A block comes from the free stack first.  Pops happen only in k_odom_model_insert and pushes
+// only in k_odom_evict, never in one launch, so the stack's entries below the counter do not change while blocks are popped: a
+// compare-and-swap that only ever lowers the counter hands each entry to one wave, and never goes below zero.
+__device__ inline int odom_alloc_block(int* next, int cap_blocks, vox_u64* counters, const int* free_stack) {
+  vox_u64 n = __atomic_load_n(&counters[4], __ATOMIC_RELAXED);
+  while (n > 0) {
+    const vox_u64 seen = atomicCAS(&counters[4], n, n - 1);
+    if (seen == n) {
+      const int r = free_stack[n - 1];
+      next[r] = -1;
+      return r;
+    }
+    n = seen;
+  }
   const vox_u64 b = atomicAdd(&counters[0], 1ULL);
   if (b >= vox_u64(cap_blocks)) {
     atomicMax(&counters[3], 1ULL);
@@ -225,7 +248,8 @@ __device__ inline int odom_alloc_block(int* next, int cap_blocks, vox_u64* count
 
 // one wave per group: candidates order[g0 .. g1) (indices into pts / covs, ascending) all lie in the voxel `keys[group]`
 __global__ __launch_bounds__(kOdomWave) void k_odom_model_insert(const double* pts, const double* covs, const int* order, const int* group_begin, const vox_u64* group_key, int groups,
-                                                                 double thresh_sq, OdomVoxel* table, unsigned mask, OdomBlock* blocks, int* next, int cap_blocks, vox_u64* counters) {
+                                                                 double thresh_sq, OdomVoxel* table, unsigned mask, OdomBlock* blocks, int* next, int cap_blocks, vox_u64* counters,
+                                                                 const int* free_stack, int lru_count) {
   const int g = blockIdx.x, lane = threadIdx.x;
   if (g >= groups) return;
   const vox_u64 key = group_key[g];
@@ -239,7 +263,7 @@ __global__ __launch_bounds__(kOdomWave) void k_odom_model_insert(const double* p
       vox_u64 old = __atomic_load_n(&table[h].key, __ATOMIC_RELAXED);
       if (old == 0) {
         if (fresh < 0) {
-          fresh = odom_alloc_block(next, cap_blocks, counters);
+          fresh = odom_alloc_block(next, cap_blocks, counters, free_stack);
           if (fresh < 0) break;  // (the full flag is set)
         }
         old = atomicCAS(&table[h].key, 0ULL, key);
@@ -257,6 +281,7 @@ __global__ __launch_bounds__(kOdomWave) void k_odom_model_insert(const double* p
       h = (h + 1) & mask;
     }
     if (!ok) atomicMax(&counters[3], 1ULL);  // no block, or (never, by the sizing above) no slot: reported, not dropped silently
+    else table[h].last_lru_count = lru_count;  // ivox.cpp:164 runs before LinearContainer::insert: a voxel whose candidates are all refused is stamped too
     s_slot = int(h), s_ok = ok;
   }
   __syncthreads();
@@ -280,7 +305,7 @@ __global__ __launch_bounds__(kOdomWave) void k_odom_model_insert(const double* p
     const int pos = count % kOdomBlockPoints;
     if (count > 0 && pos == 0) {  // the tail block is full: chain a fresh one
       if (lane == 0) {
-        s_slot = odom_alloc_block(next, cap_blocks, counters);
+        s_slot = odom_alloc_block(next, cap_blocks, counters, free_stack);
         if (s_slot >= 0) next[tail] = s_slot;
       }
       __syncthreads();
@@ -300,6 +325,41 @@ __global__ __launch_bounds__(kOdomWave) void k_odom_model_insert(const double* p
   }
 }
 
+// The LRU pass: one thread per slot of `old`.  `fresh` is zeroed, of the same size, and becomes the table.  A voxel stays iff
+// last_lru_count >= horizon (ivox.cpp:172: strictly below the horizon leaves).
+constexpr int kOdomEvictThreads = 256;
+__global__ __launch_bounds__(kOdomEvictThreads) void k_odom_evict(const OdomVoxel* old, OdomVoxel* fresh, unsigned mask, const int* next, int cap_blocks, int* free_stack, vox_u64* counters,
+                                                                  int horizon) {
+  const unsigned slot = blockIdx.x * unsigned(kOdomEvictThreads) + threadIdx.x;
+  if (slot > mask) return;
+  const OdomVoxel v = old[slot];
+  if (v.key == 0) return;
+  if (v.last_lru_count < horizon) {
+    // a chain holds max(1, ceil(count / 64)) blocks (a block is chained only for a point that enters it); the bounds keep a corrupted
+    // chain from walking off the pool or overfilling the stack
+    const int chain = v.count > 0 ? (v.count + kOdomBlockPoints - 1) / kOdomBlockPoints : 1;
+    int b = v.head;
+    for (int i = 0; i < chain && b >= 0 && b < cap_blocks; i++) {
+      const int after = next[b];
+      const vox_u64 at = atomicAdd(&counters[4], 1ULL);
+      if (at < vox_u64(cap_blocks)) free_stack[at] = b;
+      b = after;
+    }
+    atomicAdd(&counters[1], ~0ULL);  // minus one
+    atomicAdd(&counters[5], 1ULL);
+    if (v.count > 0) atomicAdd(&counters[2], 0ULL - vox_u64(v.count));
+    return;
+  }
+  unsigned h = unsigned(vox_mix(v.key)) & mask;
+  for (unsigned probes = 0; probes <= mask; probes++) {  // (keys are distinct and there are as many slots as in `old`: a slot is found)
+    if (atomicCAS(&fresh[h].key, 0ULL, v.key) == 0) {
+      fresh[h].head = v.head, fresh[h].tail = v.tail, fresh[h].count = v.count, fresh[h].last_lru_count = v.last_lru_count;
+      return;
+    }
+    h = (h + 1) & mask;
+  }
+}
+
 // ---- CT-GICP ------------------------------------------------------------------------------------------------------------------------
 struct OdomModel {
   const OdomVoxel* table;
@@ -309,8 +369,11 @@ struct OdomModel {
   double res;
 };
 
-// iVox::nearest_neighbor_search: the 7 voxels in the reference's order, `if (dist > min_dist) continue` (a tie goes to the later one)
-__device__ inline bool odom_nearest(const OdomModel& m, double x, double y, double z, int* blk, int* pos, double* dist) {
+// iVox::nearest_neighbor_search: the 7 voxels in the reference's order, `if (dist > min_dist) continue` (a tie goes to the later one).
+// Touch: every voxel found is stamped with lru_count (:223), whether or not it holds the nearest point -- lanes that find the same
+// voxel store the same value, so plain stores do; without Touch nothing is stored and the table is only read.
+template <bool Touch>
+__device__ inline bool odom_nearest(const OdomModel& m, int lru_count, double x, double y, double z, int* blk, int* pos, double* dist) {
   const double cx = floor(x / m.res), cy = floor(y / m.res), cz = floor(z / m.res);
   const double L = double(kVoxAxisLimit);
   const int off[7][3] = {{0, 0, 0}, {1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
@@ -323,6 +386,7 @@ __device__ inline bool odom_nearest(const OdomModel& m, double x, double y, doub
     const vox_u64 key = (vox_u64((long long)fx + kVoxAxisLimit) | (vox_u64((long long)fy + kVoxAxisLimit) << 21) | (vox_u64((long long)fz + kVoxAxisLimit) << 42)) + 1ULL;
     const int h = odom_find(m.table, m.mask, key);
     if (h < 0) continue;
+    if constexpr (Touch) const_cast<OdomVoxel*>(m.table)[h].last_lru_count = lru_count;
     const int count = m.table[h].count;
     int b = m.table[h].head;
     for (int base = 0; base < count; base += kOdomBlockPoints, b = m.next[b]) {
@@ -354,8 +418,9 @@ __device__ inline double odom_point_error(const double* Mh /* 3 x 3 */, const do
 }
 
 // per source point: found[i], target[i] (3), mahal[i] (9, row-major) are stored for k_odom_error; partials[wave][kOdomSums]
+template <bool Touch>
 __global__ __launch_bounds__(kOdomWave) void k_odom_linearize(const double* pts, const double* covs, const int* time_index, int M, const double* poses /* K x kOdomPoseDoubles */, OdomModel model,
-                                                              double max_dist_sq, int* found, double* target, double* mahal, double* partials) {
+                                                              double max_dist_sq, int* found, double* target, double* mahal, double* partials, int lru_count) {
   const int lane = threadIdx.x, i = blockIdx.x * kOdomWave + lane;
   double H0[3][6], H1[3][6], Mh[9], e[3], me[3], err = 0.0, cnt = 0.0;
   for (int r = 0; r < 3; r++)
@@ -370,7 +435,7 @@ __global__ __launch_bounds__(kOdomWave) void k_odom_linearize(const double* pts,
     odom_residual(P, p, zero, q);
     int blk = 0, pos = 0;
     double dist = 0.0;
-    const bool ok = odom_nearest(model, q[0], q[1], q[2], &blk, &pos, &dist) && !(dist > max_dist_sq);
+    const bool ok = odom_nearest<Touch>(model, lru_count, q[0], q[1], q[2], &blk, &pos, &dist) && !(dist > max_dist_sq);
     double tg[3] = {0.0, 0.0, 0.0};
     if (ok) {
       const OdomBlock& B = model.blocks[blk];

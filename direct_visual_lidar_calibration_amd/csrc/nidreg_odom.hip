@@ -20,8 +20,12 @@ struct nidreg_odom {
   int max_blocks = 0;      // the pool never grows past this
   int cap_blocks = 0;      // blocks allocated now
   int64_t table_cap = 0;   // slots, a power of two >= 2 x max_blocks (a voxel owns at least one block)
-  int64_t blocks = 0, voxels = 0, points = 0;
+  int64_t blocks = 0, voxels = 0, points = 0;  // blocks: handed out by the bump counter, the free ones included (what the pool must hold)
   nidreg::DeviceBuf d_table, d_blocks, d_next, d_counters;
+  // the LRU eviction (nidreg_odom_set_lru; lru_thresh = 0: off, and neither buffer below exists)
+  int32_t lru_thresh = 0, lru_cycle = 10, lru_count = 0;
+  int64_t free_blocks = 0, evicted = 0, passes = 0;
+  nidreg::DeviceBuf d_spare, d_free;  // the table the next pass fills; the stack of free block ids (max_blocks entries)
   // the current scan (nidreg_odom_set_source)
   int m = 0, max_time_index = -1, src_cap = 0;
   bool linearized = false;
@@ -33,6 +37,7 @@ namespace nidreg {
 namespace {
 
 constexpr int kInitialBlocks = 1024;
+constexpr int kCounters = 6;  // nid_odom_kernels.hpp: odom_alloc_block
 
 unsigned waves_of(int n) { return unsigned(std::max(1, (n + kOdomWave - 1) / kOdomWave)); }
 
@@ -155,10 +160,10 @@ int nidreg_odom_create(int device_id, double voxel_resolution, double insertion_
   h->table_cap = 1024;
   while (h->table_cap < 2LL * max_blocks) h->table_cap <<= 1;
   HIP_TRY(h->d_table.alloc(size_t(h->table_cap) * sizeof(OdomVoxel)));
-  HIP_TRY(h->d_counters.alloc(4 * sizeof(vox_u64)));
+  HIP_TRY(h->d_counters.alloc(kCounters * sizeof(vox_u64)));
   HIP_TRY(h->d_out.alloc(kOdomSums * 8));
   HIP_TRY(hipMemsetAsync(h->d_table.as<void>(), 0, size_t(h->table_cap) * sizeof(OdomVoxel), nullptr));
-  HIP_TRY(hipMemsetAsync(h->d_counters.as<void>(), 0, 4 * sizeof(vox_u64), nullptr));
+  HIP_TRY(hipMemsetAsync(h->d_counters.as<void>(), 0, kCounters * sizeof(vox_u64), nullptr));
   HIP_TRY(hipStreamSynchronize(nullptr));
   if (const int rc = pool_reserve(h.get(), kInitialBlocks)) return rc;
   *out = h.release();
@@ -203,7 +208,9 @@ int nidreg_odom_model_insert(nidreg_odom* h, const double* points, const double*
   const int groups = int(gkey.size());
   gbegin.push_back(m);
   HIP_TRY(hipSetDevice(h->device));
-  if (const int rc = pool_reserve(h, h->blocks + groups + m / kOdomBlockPoints)) return rc;  // an upper bound of the blocks this call takes
+  // an upper bound of the blocks this call takes, less the free ones it pops first: a handle that recycles does not grow its pool for them
+  if (const int rc = pool_reserve(h, h->blocks + std::max<int64_t>(0, int64_t(groups) + m / kOdomBlockPoints - h->free_blocks))) return rc;
+  h->lru_count++;  // ivox.cpp:144
   DeviceBuf d_pts, d_covs, d_order, d_gbegin, d_gkey;
   HIP_TRY(d_pts.alloc(size_t(m) * 24));
   HIP_TRY(d_covs.alloc(size_t(m) * 48));
@@ -217,15 +224,28 @@ int nidreg_odom_model_insert(nidreg_odom* h, const double* points, const double*
   HIP_TRY(hipMemcpy(d_gkey.as<void>(), gkey.data(), size_t(groups) * sizeof(vox_u64), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_odom_model_insert, dim3(unsigned(groups)), dim3(kOdomWave), 0, nullptr, d_pts.as<const double>(), d_covs.as<const double>(), d_order.as<const int>(),
                      d_gbegin.as<const int>(), d_gkey.as<const vox_u64>(), groups, h->thresh_sq, h->d_table.as<OdomVoxel>(), unsigned(h->table_cap - 1), h->d_blocks.as<OdomBlock>(),
-                     h->d_next.as<int>(), h->cap_blocks, h->d_counters.as<vox_u64>());
+                     h->d_next.as<int>(), h->cap_blocks, h->d_counters.as<vox_u64>(), h->d_free.as<const int>(), int(h->lru_count));
   HIP_TRY(hipGetLastError());
-  vox_u64 cnt[4];
+  // ivox.cpp:169-178: the horizon must be positive, and only every lru_cycle-th insert looks
+  const int64_t horizon = int64_t(h->lru_count) - h->lru_thresh;
+  const bool evict = h->lru_thresh > 0 && horizon > 0 && h->lru_count % h->lru_cycle == 0;
+  if (evict) {
+    HIP_TRY(hipMemsetAsync(h->d_spare.as<void>(), 0, size_t(h->table_cap) * sizeof(OdomVoxel), nullptr));
+    hipLaunchKernelGGL(k_odom_evict, dim3(unsigned((h->table_cap + kOdomEvictThreads - 1) / kOdomEvictThreads)), dim3(kOdomEvictThreads), 0, nullptr, h->d_table.as<const OdomVoxel>(),
+                       h->d_spare.as<OdomVoxel>(), unsigned(h->table_cap - 1), h->d_next.as<const int>(), h->cap_blocks, h->d_free.as<int>(), h->d_counters.as<vox_u64>(), int(horizon));
+    HIP_TRY(hipGetLastError());
+  }
+  vox_u64 cnt[kCounters];
   HIP_TRY(hipMemcpy(cnt, h->d_counters.as<void>(), sizeof(cnt), hipMemcpyDeviceToHost));
+  if (evict) {  // (the copy above waited for the pass)
+    std::swap(h->d_table, h->d_spare);
+    h->passes++;
+  }
   h->blocks = int64_t(std::min<vox_u64>(cnt[0], vox_u64(h->cap_blocks)));
-  h->voxels = int64_t(cnt[1]), h->points = int64_t(cnt[2]);
+  h->voxels = int64_t(cnt[1]), h->points = int64_t(cnt[2]), h->free_blocks = int64_t(cnt[4]), h->evicted = int64_t(cnt[5]);
   if (cnt[3]) {
     cnt[0] = vox_u64(h->blocks), cnt[3] = 0;
-    HIP_TRY(hipMemcpy(h->d_counters.as<void>(), cnt, sizeof(cnt), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_counters.as<void>(), cnt, 4 * sizeof(vox_u64), hipMemcpyHostToDevice));
     return fail(NIDREG_ERR_FULL, std::string(who) + ": the pool of " + std::to_string(h->max_blocks) + " point blocks is exhausted; points of this scan were left out of the model");
   }
   return NIDREG_OK;
@@ -233,7 +253,29 @@ int nidreg_odom_model_insert(nidreg_odom* h, const double* points, const double*
 
 int nidreg_odom_model_info(nidreg_odom* h, int64_t* info4) {
   if (!h || !info4) return fail(NIDREG_ERR_INVALID, "nidreg_odom_model_info: null argument");
-  info4[0] = h->voxels, info4[1] = h->points, info4[2] = h->blocks, info4[3] = h->max_blocks;
+  info4[0] = h->voxels, info4[1] = h->points, info4[2] = h->blocks - h->free_blocks, info4[3] = h->max_blocks;
+  return NIDREG_OK;
+}
+
+int nidreg_odom_set_lru(nidreg_odom* h, int32_t lru_thresh, int32_t lru_cycle) {
+  const char* const who = "nidreg_odom_set_lru";
+  if (!h) return fail(NIDREG_ERR_INVALID, std::string(who) + ": null handle");
+  if (lru_thresh < 0) return fail(NIDREG_ERR_INVALID, std::string(who) + ": lru_thresh must be >= 0 (0: no eviction)");
+  if (lru_cycle < 1) return fail(NIDREG_ERR_INVALID, std::string(who) + ": lru_cycle must be >= 1");
+  // a model must not carry stamps from before the rule was set
+  if (h->lru_count > 0) return fail(NIDREG_ERR_INVALID, std::string(who) + ": the model has been inserted into; the eviction rule is set before the first nidreg_odom_model_insert");
+  if (lru_thresh > 0 && !h->d_spare.as<void>()) {
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(h->d_spare.alloc(size_t(h->table_cap) * sizeof(OdomVoxel)));
+    HIP_TRY(h->d_free.alloc(size_t(h->max_blocks) * sizeof(int)));
+  }
+  h->lru_thresh = lru_thresh, h->lru_cycle = lru_cycle;
+  return NIDREG_OK;
+}
+
+int nidreg_odom_lru_info(nidreg_odom* h, int64_t* info4) {
+  if (!h || !info4) return fail(NIDREG_ERR_INVALID, "nidreg_odom_lru_info: null argument");
+  info4[0] = h->lru_count, info4[1] = h->evicted, info4[2] = h->free_blocks, info4[3] = h->passes;
   return NIDREG_OK;
 }
 
@@ -311,8 +353,11 @@ int nidreg_odom_linearize(nidreg_odom* h, const double* poses, int32_t num_poses
   h->linearized = true;
   if (h->m == 0) return NIDREG_OK;
   const unsigned waves = waves_of(h->m);
-  hipLaunchKernelGGL(k_odom_linearize, dim3(waves), dim3(kOdomWave), 0, nullptr, h->d_pts.as<const double>(), h->d_covs.as<const double>(), h->d_tidx.as<const int>(), h->m,
-                     h->d_poses.as<const double>(), model_of(h), max_correspondence_dist_sq, h->d_found.as<int>(), h->d_target.as<double>(), h->d_mahal.as<double>(), h->d_partials.as<double>());
+  with_bool(h->lru_thresh > 0, [&](auto Touch) {  // with the eviction on, the search stamps the voxels it finds; off, it stores nothing
+    hipLaunchKernelGGL((k_odom_linearize<decltype(Touch)::value>), dim3(waves), dim3(kOdomWave), 0, nullptr, h->d_pts.as<const double>(), h->d_covs.as<const double>(), h->d_tidx.as<const int>(),
+                       h->m, h->d_poses.as<const double>(), model_of(h), max_correspondence_dist_sq, h->d_found.as<int>(), h->d_target.as<double>(), h->d_mahal.as<double>(),
+                       h->d_partials.as<double>(), int(h->lru_count));
+  });
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_odom_sum, dim3(1), dim3(128), 0, nullptr, h->d_partials.as<const double>(), int(waves), kOdomSums, h->d_out.as<double>());
   HIP_TRY(hipGetLastError());

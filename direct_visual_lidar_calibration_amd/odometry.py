@@ -24,7 +24,9 @@ device does the rest.  Differences from the reference, all deliberate:
   iteration order is not reproducible across standard libraries); its rules are kept;
 * the optimiser restates gtsam's Levenberg-Marquardt from its documented defaults; gtsam itself is not available, so it is
   UNPINNED against it;
-* the model only grows: iVox's LRU eviction (``lru_thresh`` = 100 scans) is not built;
+* iVox's LRU eviction (``lru_thresh`` = 100 scans, looked at on every 10th insert; ivox.cpp:144-178, :223) runs on the device and
+  is checked against a restatement of that rule (tests/odometry_lru_oracle.py) that is itself UNPINNED against a compiled
+  ``ivox.cpp``; its "too many voxels" branch (2^32 - 1 voxels) is not built, and ``lru_thresh=0`` keeps a model that only grows;
 * the voxel insert evaluates ``interpolateRt`` per point (the reference refreshes the pose every 1e-4 of normalised time), and
   within a frame the point with the highest message index wins a voxel (the reference: the latest in time);
 * where the reference divides by zero: a frame whose largest time is <= 0 uses t = 0 for every point, a scan duration <= 0 gives
@@ -229,13 +231,26 @@ def _check(rc, what):
 class DeviceBackend:
     """The ``nidreg_odom_*`` handle: the model and the current scan on the GPU.  No CPU implementation stands behind it."""
 
-    def __init__(self, device=0, voxel_resolution=1.0, insertion_dist_thresh=0.05, max_blocks=1 << 18):
+    def __init__(self, device=0, voxel_resolution=1.0, insertion_dist_thresh=0.05, max_blocks=1 << 18, lru_thresh=0, lru_cycle=10):
+        """``lru_thresh`` > 0: a voxel neither inserted into nor found by a search for more than ``lru_thresh`` inserts leaves the model
+        on the next insert whose count is a multiple of ``lru_cycle`` (iVox's rule); 0: the model only grows"""
         self._lib = _lib.load()
         self._h = None
         h = ctypes.c_void_p()
         _check(self._lib.nidreg_odom_create(int(device), float(voxel_resolution), float(insertion_dist_thresh), int(max_blocks), ctypes.byref(h)), "nidreg_odom_create")
         self._h = h
         self._m = 0
+        if (int(lru_thresh), int(lru_cycle)) != (0, 10):
+            self.set_lru(lru_thresh, lru_cycle)
+
+    def set_lru(self, lru_thresh, lru_cycle=10):
+        """``nidreg_odom_set_lru``: before the first ``model_insert`` only"""
+        _check(self._lib.nidreg_odom_set_lru(self._h, int(lru_thresh), int(lru_cycle)), "nidreg_odom_set_lru")
+
+    def lru_info(self):
+        v = (ctypes.c_int64 * 4)()
+        _check(self._lib.nidreg_odom_lru_info(self._h, v), "nidreg_odom_lru_info")
+        return {"lru_count": int(v[0]), "evicted_voxels": int(v[1]), "free_blocks": int(v[2]), "passes": int(v[3])}
 
     def knn_covariances(self, points, k):
         """``(neighbors (m, k) int32, normals (m, 3), covs (m, 6))``"""
@@ -427,9 +442,9 @@ class DynamicPointCloudIntegrator:
     ``info``, ``close``) and ``poses()``.  Defaults as the reference's (:22-30).  Unlike the static integrator of
     ``preprocess_ros1`` it applies ``min_distance`` -- in the odometry frame, as the reference does (:149)."""
 
-    def __init__(self, voxel_resolution=0.05, min_distance=1.0, device=0, k_neighbors=20, target_num_points=10000, seed=0, max_blocks=1 << 18):
+    def __init__(self, voxel_resolution=0.05, min_distance=1.0, device=0, k_neighbors=20, target_num_points=10000, seed=0, max_blocks=1 << 18, lru_thresh=100):
         self._grid = preprocess.StaticPointCloudIntegrator(voxel_resolution, min_distance, device)
-        self._backend = DeviceBackend(device, max_blocks=max_blocks)
+        self._backend = DeviceBackend(device, max_blocks=max_blocks, lru_thresh=lru_thresh)  # iVox(1.0, 0.05, 100): lru_cycle stays 10
         self._matcher = ScanMatcher(self._backend, k_neighbors)
         self._lib = self._grid._lib
         self.target_num_points = int(target_num_points)
@@ -476,9 +491,10 @@ class DynamicPointCloudIntegrator:
         return list(self._poses)
 
     def info(self):
-        """The voxel grid's ``info()`` plus ``{"model": the model's voxels / points / blocks, "frames"}``"""
+        """The voxel grid's ``info()`` plus ``{"model": the model's voxels / points / blocks, "lru": the eviction's totals, "frames"}``"""
         out = self._grid.info()
         out["model"] = self._backend.model_info()
+        out["lru"] = self._backend.lru_info()
         out["frames"] = len(self._poses)
         return out
 

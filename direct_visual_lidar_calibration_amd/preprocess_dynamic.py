@@ -7,7 +7,8 @@ running model with continuous-time GICP and deskewed, and all raw points go into
 ``preprocess_ros1.run`` with ``odometry.DynamicPointCloudIntegrator`` in the place of the static integrator: the same options, topics,
 camera parameters, per-bag outputs and ``calib.json`` (``preprocess_ros1`` lists the differences from the reference; ``odometry`` those of
 the integrator).  ``--k_neighbors`` is used here; ``--target_num_points`` and ``--seed`` (the scan sampler's) are extensions: the reference
-fixes 10000 and seeds ``std::mt19937`` by default.  ``-d`` is accepted and implied.  ``--min_distance`` is honoured, in the odometry frame.
+fixes 10000 and seeds ``std::mt19937`` by default; ``--lru_thresh`` (the model forgets a voxel unused for that many scans; 0: never) is
+an extension too: the reference fixes 100.  ``-d`` is accepted and implied.  ``--min_distance`` is honoured, in the odometry frame.
 """
 import functools
 import sys
@@ -22,6 +23,8 @@ def build_parser():
     p.description = "preprocess with dynamic LiDAR integration"
     p.add_argument("--target_num_points", type=int, default=10000, help="points a scan is sampled down to for the registration")
     p.add_argument("--seed", type=int, default=0, help="seed of the scan sampler")
+    p.add_argument("--lru_thresh", type=int, default=100, help="extension: scans after which the registration model drops a voxel it neither inserted into nor searched "
+                   "(the reference fixes 100); 0 keeps every voxel")
     return p
 
 
@@ -30,7 +33,9 @@ def run(args, **kw):
         raise ValueError(f"error: --k_neighbors {args.k_neighbors}: 2..32 neighbours are supported")
     if args.target_num_points < args.k_neighbors:
         raise ValueError(f"error: --target_num_points {args.target_num_points} is below --k_neighbors {args.k_neighbors}")
-    factory = functools.partial(odometry.DynamicPointCloudIntegrator, k_neighbors=args.k_neighbors, target_num_points=args.target_num_points, seed=args.seed)
+    if args.lru_thresh < 0:
+        raise ValueError(f"error: --lru_thresh {args.lru_thresh}: must be >= 0 (0 disables the eviction)")
+    factory = functools.partial(odometry.DynamicPointCloudIntegrator, k_neighbors=args.k_neighbors, target_num_points=args.target_num_points, seed=args.seed, lru_thresh=args.lru_thresh)
     return preprocess_ros1.run(args, integrator_factory=factory, **kw)
 
 

@@ -404,8 +404,18 @@ void nidreg_integrator_destroy(nidreg_integrator* h);
  * to run.  Points are x y z (3 doubles), covariances xx xy xz yy yz zz (6 doubles).
  *   nidreg_odom_create        the model: iVox(voxel_resolution, insertion_dist_thresh) (src/vlcal/common/ivox.cpp; the reference uses
  *                             1.0 and 0.05) -- a hash of voxels under the integrator's packed 64-bit key, each voxel an ordered list of
- *                             points in chained blocks of 64 from a pool that grows up to max_blocks (1..2^24; 4.6 KB a block).  NOT
- *                             built: the LRU eviction (lru_thresh); the model only grows.
+ *                             points in chained blocks of 64 from a pool that grows up to max_blocks (1..2^24; 4.6 KB a block).  The
+ *                             LRU eviction is off until nidreg_odom_set_lru turns it on: the model then only grows.
+ *   nidreg_odom_set_lru       iVox's lru_thresh and lru_cycle (the reference: 100 and 10; ivox.cpp:144-178, :223).  Every
+ *                             nidreg_odom_model_insert that reaches the device raises lru_count by one and stamps the voxels it offers
+ *                             a point to (a refused point included); nidreg_odom_linearize stamps every face-neighbour voxel its search
+ *                             finds.  After an insert with lru_count - lru_thresh > 0 and lru_count % lru_cycle == 0, every voxel whose
+ *                             stamp is < lru_count - lru_thresh leaves the model and its blocks are handed out again before the pool
+ *                             grows.  lru_thresh = 0 (the state after create): off, nothing is stamped by a search.  NIDREG_ERR_INVALID
+ *                             for lru_thresh < 0, lru_cycle < 1, or after the first insert (a model must not carry stamps that were
+ *                             never written).  NOT built: the reference's "too many voxels" branch (:181-197; 2^32 - 1 voxels).  A call
+ *                             with m = 0 does not reach the device and does not count (the reference counts it).
+ *   nidreg_odom_lru_info      [0] lru_count, [1] voxels evicted in total, [2] free blocks now, [3] eviction passes run
  *   nidreg_odom_knn_covariances  for m points the k nearest of each among them (itself included; 2 <= k <= 32 and k <= m, else
  *                             NIDREG_ERR_INVALID), ordered by ascending (squared distance, index), into neighbors (m x k, nullable);
  *                             then CloudCovarianceEstimation::estimate(points, neighbors) (cloud_covariance_estimation.cpp:77-112): the
@@ -418,7 +428,7 @@ void nidreg_integrator_destroy(nidreg_integrator* h);
  *                             this call are then missing from the model: never silently).  A voxel enters the table only with its
  *                             first block (the table has >= 2 x max_blocks slots, so it stays at most half full), so a dry pool
  *                             leaves nothing behind and every later call that still needs a block reports NIDREG_ERR_FULL again.
- *   nidreg_odom_model_info    [0] voxels, [1] points, [2] blocks in use, [3] max_blocks
+ *   nidreg_odom_model_info    [0] voxels, [1] points, [2] blocks in use (handed out and not free), [3] max_blocks
  *   nidreg_odom_model_get     every point of the model: voxels in ascending key order, a voxel's points in list order
  *   nidreg_odom_set_source    the scan's sampled points, their covariances and time-table indices (>= 0), uploaded once per scan
  *   nidreg_odom_linearize     IntegratedCT_GICPFactor_::linearize (include/vlcal/common/integrated_ct_gicp_factor_impl.hpp:70-177).  poses:
@@ -446,6 +456,8 @@ int nidreg_odom_knn_covariances(nidreg_odom* h, const double* points, int32_t m,
 int nidreg_odom_covariances(nidreg_odom* h, const double* points, int32_t m, int32_t k, const int32_t* neighbors, double* normals, double* covs);
 int nidreg_odom_model_insert(nidreg_odom* h, const double* points, const double* covs, int32_t m);
 int nidreg_odom_model_info(nidreg_odom* h, int64_t* info4);
+int nidreg_odom_set_lru(nidreg_odom* h, int32_t lru_thresh, int32_t lru_cycle);
+int nidreg_odom_lru_info(nidreg_odom* h, int64_t* info4);
 int nidreg_odom_model_get(nidreg_odom* h, int32_t* voxels /* points x 3 */, double* points /* points x 3 */, double* covs /* points x 6, nullable */);
 int nidreg_odom_set_source(nidreg_odom* h, const double* points, const double* covs, const int32_t* time_index, int32_t m);
 int nidreg_odom_linearize(nidreg_odom* h, const double* poses /* num_poses x 84 */, int32_t num_poses, double max_correspondence_dist_sq, double* out122);
