@@ -77,6 +77,7 @@ EXPORTS = [
     "nidreg_odom_create", "nidreg_odom_destroy", "nidreg_odom_knn_covariances", "nidreg_odom_covariances", "nidreg_odom_model_insert", "nidreg_odom_model_info", "nidreg_odom_model_get", "nidreg_odom_set_lru", "nidreg_odom_lru_info",
     "nidreg_odom_set_source", "nidreg_odom_linearize", "nidreg_odom_error", "nidreg_odom_correspondences", "nidreg_odom_deskew_insert",
     "nidreg_features_detect", "nidreg_features_match",
+    "nidreg_splat_create", "nidreg_splat_set_colors", "nidreg_splat_draw", "nidreg_splat_destroy",
 ]
 
 _lib = None
@@ -175,6 +176,12 @@ def load():
     c_uint8_p, c_uint32_p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32)
     lib.nidreg_features_detect.argtypes = [ctypes.c_int, c_uint8_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_uint8_p, ctypes.c_int64] + [ctypes.c_int] * 5 + [c_int32_p, c_uint32_p, c_int32_p]
     lib.nidreg_features_match.argtypes = [ctypes.c_int, c_uint32_p, ctypes.c_int, c_uint32_p, ctypes.c_int] + [ctypes.c_int] * 3 + [c_int32_p] * 3
+    lib.nidreg_splat_create.argtypes = [ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p)]
+    lib.nidreg_splat_set_colors.argtypes = [ctypes.c_void_p, c_uint8_p]
+    lib.nidreg_splat_draw.argtypes = [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_double_p, ctypes.c_int, c_uint8_p, ctypes.c_int64,
+                                      ctypes.c_int, c_uint8_p, c_int32_p]
+    lib.nidreg_splat_destroy.restype = None
+    lib.nidreg_splat_destroy.argtypes = [ctypes.c_void_p]
     lib.nidreg_rccl_unique_id.argtypes = [ctypes.c_char_p]
     lib.nidreg_shard_comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]
     lib.nidreg_shard_attach_rccl.argtypes = [ctypes.c_void_p, ctypes.c_void_p]

@@ -74,6 +74,7 @@ __global__ __launch_bounds__(256) void k_lidar_zmin(
   }
 }
 
+#ifndef NID_RENDER_FRONT_END_ONLY  // (defined by a translation unit that takes point_to_pixel only: nidreg_splat.hip)
 __global__ __launch_bounds__(256) void k_lidar_argmax(
   const double* __restrict__ pts, long long stride_d, long long n, IsoParams<double> iso, const int* __restrict__ pix, const u64* __restrict__ zmin, int* __restrict__ index_image) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -95,5 +96,6 @@ __global__ __launch_bounds__(256) void k_lidar_resolve(const double* __restrict_
   const int i = index_image[q];
   intensity_image[q] = i >= 0 ? intensities[i] : 0.0;
 }
+#endif  // NID_RENDER_FRONT_END_ONLY
 
 }  // namespace nidreg

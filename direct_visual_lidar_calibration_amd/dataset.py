@@ -8,6 +8,7 @@ here                                    reference
                                         ``<bag>.png`` via ``cv::imread(.., 0)`` + ``<bag>.ply`` via ``glk::load_ply``
 ``read_ply`` / ``write_ply``            ``glk::load_ply`` / ``glk::save_ply_binary`` (Iridescence, not in the tree);
                                         the writer emits what preprocess.cpp:161-169 hands it: float x y z + float intensity
+``write_ply_colored``                   no counterpart: float x y z + uchar red green blue, what the headless viewer saves
 ``read_pcd``                            ``pcl::io::load`` of a PCD map into ``PointXYZI`` (PCL, not in the tree; preprocess_map.cpp:129-131)
 ``read_png_gray`` / ``write_png_gray``  ``cv::imread(path, 0)`` / ``cv::imwrite`` for 8-bit single-channel PNGs
 ``read_calib`` / ``write_calib``        ``calib.json`` (preprocess.cpp:220-232; calibrate.cpp:36-46, 56-65, 128-140)
@@ -168,6 +169,24 @@ def write_ply(path, points, intensities):
     rec["x"], rec["y"], rec["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
     rec["intensity"] = np.asarray(intensities)
     header = f"ply\nformat binary_little_endian 1.0\nelement vertex {n}\nproperty float x\nproperty float y\nproperty float z\nproperty float intensity\nend_header\n"
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(rec.tobytes())
+
+
+def write_ply_colored(path, points, rgb8):
+    """binary_little_endian PLY with float x y z + uchar red green blue per vertex (the headless viewer's ``--save_ply``); any PLY
+    viewer shows it.  ``read_ply`` reads its positions back."""
+    pts = np.asarray(points)
+    rgb = np.asarray(rgb8, dtype=np.uint8).reshape(-1, 3)
+    n = pts.shape[0]
+    if rgb.shape[0] != n:
+        raise ValueError("write_ply_colored: one RGB colour per point expected")
+    rec = np.empty(n, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    rec["x"], rec["y"], rec["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
+    rec["red"], rec["green"], rec["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    header = (f"ply\nformat binary_little_endian 1.0\nelement vertex {n}\nproperty float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
         f.write(rec.tobytes())

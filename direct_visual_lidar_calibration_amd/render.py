@@ -10,6 +10,9 @@ here                                        reference
 ``equalize_intensities(intensities)``       the rank equalisation loop (preprocess.cpp:464-473)
 ``colormap_turbo(x)``                       ``glk::colormapf(glk::COLORMAP::TURBO, x)`` (Iridescence, not in
                                             the reference tree: polynomial fit of the TURBO map, display only)
+``SplatRenderer(points)`` / ``.draw(..)``   what the OpenGL window of ``viewer.cpp`` / ``VisualLiDARVisualizer`` shows, as
+                                            an image: a z-buffered point-splat renderer (no counterpart in the tree)
+``quantize_colors(rgba_f32)``               the float RGBA of ``PointsColorUpdater.update`` / ``colormap_turbo`` as RGBA8
 ==========================================  =========================================================
 
 All per-point work runs in the HIP library behind ``include/nidreg.h``; no CPU implementation exists here.
@@ -114,3 +117,70 @@ def equalize_intensities(intensities, device=0):
     rc = _lib.load().nidreg_equalize_intensities(device, _dp(a), a.shape[0])
     _lib.check(rc, "nidreg_equalize_intensities")
     return a
+
+
+def quantize_colors(rgba_f32):
+    """RGBA8 of float colours in [0, 1]: ``floor(c * 255 + 0.5)`` clipped to 0..255 -- the bridge from ``PointsColorUpdater.update``
+    and ``colormap_turbo`` to ``SplatRenderer.set_colors``.  Computed in float64 (the product is exact there)."""
+    c = np.asarray(rgba_f32, dtype=np.float64)
+    return np.clip(np.floor(c * 255.0 + 0.5), 0.0, 255.0).astype(np.uint8)
+
+
+class SplatRenderer:
+    """Headless stand-in for the reference viewer's 3-D view (``viewer.cpp``, ``VisualLiDARVisualizer``): the cloud goes to the
+    device once, ``set_colors`` gives every point an RGBA8 colour, and each ``draw`` renders it through a camera model at a pose as
+    depth-tested squares of ``2 * radius + 1`` pixels (``include/nidreg.h``: nearest by float32 squared distance, the largest index
+    among equals; integer blending over ``background``)."""
+
+    def __init__(self, points, device=0):
+        pts = np.asarray(points, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] != 4:
+            raise ValueError("SplatRenderer: points must be (n, 4) homogeneous doubles")
+        if pts.shape[0] and (pts.strides[1] != 8 or pts.strides[0] < 32 or pts.strides[0] % 8):
+            pts = np.ascontiguousarray(pts)
+        self.num_points = pts.shape[0]
+        h = ctypes.c_void_p()
+        rc = _lib.load().nidreg_splat_create(device, self.num_points, _dp(pts), pts.strides[0] if self.num_points else 32, ctypes.byref(h))
+        _lib.check(rc, "nidreg_splat_create")
+        self._h = h
+
+    def set_colors(self, rgba8):
+        c = np.ascontiguousarray(rgba8, dtype=np.uint8).reshape(-1, 4)
+        if c.shape[0] != self.num_points:
+            raise ValueError("SplatRenderer.set_colors: one RGBA8 colour per point expected")
+        _lib.check(_lib.load().nidreg_splat_set_colors(self._h, c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))), "nidreg_splat_set_colors")
+
+    def draw(self, proj, image_size, T_view_lidar, radius=1, background=None, alpha=255, min_nz=None):
+        """Returns ``(rgb uint8 (H, W, 3), index int32 (H, W))``; index = the point drawn at the pixel, -1 where there is none.
+        ``background``: (H, W, 3) uint8 (rows may be padded) or ``None`` = black.  ``min_nz`` defaults to
+        ``cos(estimate_camera_fov + 0.5 deg)`` like ``PointsColorUpdater``."""
+        w, h = int(image_size[0]), int(image_size[1])
+        if min_nz is None:
+            min_nz = math.cos(estimate_camera_fov(proj, (w, h)) + 0.5 * math.pi / 180.0)
+        T = np.ascontiguousarray(np.asarray(T_view_lidar, dtype=np.float64).reshape(4, 4))
+        bg, bg_stride = None, 0
+        if background is not None:
+            bg = np.asarray(background, dtype=np.uint8)
+            if bg.shape != (h, w, 3):
+                raise ValueError("SplatRenderer.draw: background must be (H, W, 3) uint8")
+            if bg.strides[2] != 1 or bg.strides[1] != 3 or bg.strides[0] < 3 * w:
+                bg = np.ascontiguousarray(bg)
+            bg_stride = bg.strides[0]
+        u8p = ctypes.POINTER(ctypes.c_uint8)
+        rgb = np.empty((max(h, 0), max(w, 0), 3), dtype=np.uint8)
+        idx = np.empty((max(h, 0), max(w, 0)), dtype=np.int32)
+        rc = _lib.load().nidreg_splat_draw(self._h, proj.model_id, _dp(proj._intr5), _dp(proj._dist8), w, h, float(min_nz), _dp(T), int(radius),
+                                           None if bg is None else bg.ctypes.data_as(u8p), bg_stride, int(alpha), rgb.ctypes.data_as(u8p), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+        _lib.check(rc, "nidreg_splat_draw")
+        return rgb, idx
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.load().nidreg_splat_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

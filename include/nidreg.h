@@ -342,6 +342,37 @@ int nidreg_generate_lidar_image(int model_id, const double* intrinsics, const do
  * reference's std::sort leaves that order unspecified). */
 int nidreg_equalize_intensities(int device_id, double* intensities, int64_t num_points);
 
+/* ---- headless viewer: a z-buffered point-splat renderer (csrc/nid_splat_kernels.hpp) ------------------------------------------
+ * The reference shows a result in an OpenGL window (src/viewer.cpp; VisualLiDARVisualizer; the colours come from
+ * PointsColorUpdater::update, src/vlcal/common/points_color_updater.cpp:37-61).  This is the part of it that makes a picture, without
+ * a window: every point is a (2 radius + 1)^2 square of pixels around the pixel it projects to, depth-tested.
+ *   nidreg_splat_create      uploads the cloud once ((x y z w) doubles, byte stride >= 32): one upload serves every view of a bag.
+ *                            num_points = 0 is valid.
+ *   nidreg_splat_set_colors  num_points x RGBA8 (host); may be called again between draws.
+ *   nidreg_splat_draw        point i goes through the front end of PointsColorUpdater::update / generate_lidar_image under
+ *                            T_view_lidar (row-major 4x4) and the given camera: FoV gate (normalised z >= min_nz), projection,
+ *                            truncating cast, in-image test.  A point that fails it draws NOTHING, even where its square would reach
+ *                            into the image.  Its depth is d = float(squared camera-frame distance), rounded to nearest (non-finite:
+ *                            nothing drawn); per covered pixel inside the image the smallest
+ *                                (bits(d) << 32) | (0xFFFFFFFF - i)
+ *                            wins: the nearest point in float32 and, among equal float32 depths, the LARGEST index (the tie direction
+ *                            of nidreg_generate_lidar_image; depths that differ only in fp64 are equal here).  Then per pixel, in
+ *                            integers: a = (alpha * A_i + 127) / 255, channel = (background * (255 - a) + C_i * a + 127) / 255;
+ *                            a pixel nothing covers keeps the background.  background_rgb: height rows of 3 * width bytes,
+ *                            background_row_stride bytes apart (0: packed), or NULL = black.  out_rgb: height x width x 3 bytes;
+ *                            out_index (nullable): height x width int32, the winning point or -1.  Every draw starts from an empty
+ *                            depth buffer.  The picture is the same bytes from run to run and equals tests/viewer_oracle.py.
+ * NIDREG_ERR_INVALID with a message, before the device is touched and with nothing written: num_points above 2^31 - 1 or negative,
+ * a point stride that is no multiple of 8 or below 32, radius outside [0, 8], alpha outside [0, 255], a non-positive width or height
+ * or width * height beyond int, a background row stride below 3 * width, an unknown model, a NULL array, a draw of a non-empty cloud
+ * before any colours were set. */
+typedef struct nidreg_splat nidreg_splat;
+int nidreg_splat_create(int device_id, int64_t num_points, const double* points, int64_t point_stride, nidreg_splat** out);
+int nidreg_splat_set_colors(nidreg_splat* s, const uint8_t* rgba);
+int nidreg_splat_draw(nidreg_splat* s, int model_id, const double* intrinsics, const double* distortion, int width, int height, double min_nz, const double* T_view_lidar, int radius,
+                      const uint8_t* background_rgb /* nullable */, int64_t background_row_stride, int alpha, uint8_t* out_rgb, int32_t* out_index /* nullable */);
+void nidreg_splat_destroy(nidreg_splat* s);
+
 /* ---- voxel integrator: vlcal::StaticPointCloudIntegrator (src/vlcal/preprocess/static_point_cloud_integrator.cpp) -------------
  * A hash table of voxels on the device (csrc/nid_voxel_kernels.hpp).  The reference's loop (:25-37), per point in order: skip it when
  * sqrt(x^2 + y^2 + z^2) < min_distance; voxel = floor(x / res), floor(y / res), floor(z / res) in double (a true division and a
