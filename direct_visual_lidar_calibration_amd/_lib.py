@@ -24,6 +24,8 @@ IMAGE_F64, IMAGE_U8 = 0, 1
 FLAG_INPUT_ORDER = 1
 FLAG_EXT_STREAM = 2
 FLAG_NEAREST_EXACT = 4
+JPEG_GRAY_LUMA, JPEG_GRAY_BGR = 0, 1  # NIDREG_JPEG_GRAY_*
+JPEG_SUB_GRAY, JPEG_SUB_444, JPEG_SUB_422, JPEG_SUB_420 = 0, 1, 2, 3  # NIDREG_JPEG_SUB_*
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
@@ -78,6 +80,7 @@ EXPORTS = [
     "nidreg_odom_set_source", "nidreg_odom_linearize", "nidreg_odom_error", "nidreg_odom_correspondences", "nidreg_odom_deskew_insert",
     "nidreg_features_detect", "nidreg_features_match",
     "nidreg_splat_create", "nidreg_splat_set_colors", "nidreg_splat_draw", "nidreg_splat_destroy",
+    "nidreg_jpeg_info", "nidreg_jpeg_coefficients", "nidreg_jpeg_decode_gray", "nidreg_jpeg_get_timing",
 ]
 
 _lib = None
@@ -182,6 +185,10 @@ def load():
                                       ctypes.c_int, c_uint8_p, c_int32_p]
     lib.nidreg_splat_destroy.restype = None
     lib.nidreg_splat_destroy.argtypes = [ctypes.c_void_p]
+    lib.nidreg_jpeg_info.argtypes = [ctypes.c_char_p, ctypes.c_int64] + [c_int32_p] * 5
+    lib.nidreg_jpeg_coefficients.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int16), ctypes.c_int64, ctypes.POINTER(ctypes.c_uint16)]
+    lib.nidreg_jpeg_decode_gray.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_int64, ctypes.c_int, c_uint8_p, ctypes.c_int64]
+    lib.nidreg_jpeg_get_timing.argtypes = [c_double_p]
     lib.nidreg_rccl_unique_id.argtypes = [ctypes.c_char_p]
     lib.nidreg_shard_comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]
     lib.nidreg_shard_attach_rccl.argtypes = [ctypes.c_void_p, ctypes.c_void_p]

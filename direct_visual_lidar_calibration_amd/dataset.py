@@ -11,11 +11,16 @@ here                                    reference
 ``write_ply_colored``                   no counterpart: float x y z + uchar red green blue, what the headless viewer saves
 ``read_pcd``                            ``pcl::io::load`` of a PCD map into ``PointXYZI`` (PCL, not in the tree; preprocess_map.cpp:129-131)
 ``read_png_gray`` / ``write_png_gray``  ``cv::imread(path, 0)`` / ``cv::imwrite`` for 8-bit single-channel PNGs
+``read_image_gray``                     ``cv::imread(path, 0)`` for a camera photograph (preprocess_map.cpp:69): PNG as above, or a baseline
+                                        JPEG -- the Y plane, then the EXIF orientation -- decoded on the GPU (``decode_jpeg_gray``)
+``decode_jpeg_gray``                    libjpeg as OpenCV drives it, in the two ways the reference does: ``cv::imread(path, 0)`` (LUMA) and
+                                        ``cv_bridge::toCvCopy(msg, "mono8")`` (BGR, preprocess_ros1.cpp:104-134); unpinned against OpenCV itself
 ``read_calib`` / ``write_calib``        ``calib.json`` (preprocess.cpp:220-232; calibrate.cpp:36-46, 56-65, 128-140)
 ``init_T_lidar_camera(config)``         calibrate.cpp:56-77 (manual guess first, then the automatic one)
 ======================================  ==============================================================
 
-Pure host code (numpy + zlib + json); nothing here is on the per-evaluation path.
+Pure host code (numpy + zlib + json) except the JPEG decoder, whose arithmetic runs on the GPU (``nidreg_jpeg_decode_gray``); nothing
+here is on the per-evaluation path.
 """
 import functools
 import json
@@ -428,6 +433,86 @@ def write_png_gray(path, image):
     if img.ndim != 2:
         raise ValueError("write_png_gray: single-channel image expected")
     write_png(path, img)
+
+
+# --------------------------------------------------------------------------------------------- JPEG
+JPEG_GRAY_LUMA, JPEG_GRAY_BGR = 0, 1  # NIDREG_JPEG_GRAY_*
+_JPEG_REFUSAL = "JPEG images are not decoded here"
+
+
+def _jpeg_refusal(path, message):
+    """``error: failed to load image <where>: JPEG images are not decoded here unless ... (<reason>)`` from the library's error text"""
+    at = message.find(_JPEG_REFUSAL)
+    return ValueError(f"error: failed to load image {path}: {message[at:] if at >= 0 else message}")
+
+
+def jpeg_info(data, path="JPEG data"):
+    """``nidreg_jpeg_info`` (host only): ``(width, height, components, subsampling, exif_orientation)``; a stream outside the
+    decoder's scope raises ``ValueError`` with the reason"""
+    import ctypes
+
+    from . import _lib
+
+    lib = _lib.load()
+    data = bytes(data)
+    out = [ctypes.c_int32() for _ in range(5)]
+    rc = lib.nidreg_jpeg_info(data, len(data), *[ctypes.byref(v) for v in out])
+    if rc == _lib.NIDREG_ERR_INVALID:
+        raise _jpeg_refusal(path, _lib.last_error())
+    _lib.check(rc, "nidreg_jpeg_info")
+    return tuple(int(v.value) for v in out)
+
+
+def decode_jpeg_gray(data, mode, device=0, path="JPEG data"):
+    """A baseline JPEG stream as an (H, W) uint8 gray image, decoded on the GPU (``nidreg_jpeg_decode_gray``; the entropy decode
+    runs on the host first).  ``mode``: ``JPEG_GRAY_LUMA`` is ``cv::imread(path, 0)`` -- the Y plane --, ``JPEG_GRAY_BGR`` is
+    ``cv_bridge::toCvCopy(msg, "mono8")`` -- decode to BGR, then OpenCV's fixed-point luma; the two differ for colour streams.
+    No EXIF orientation is applied (``read_image_gray`` does that).  A stream outside the decoder's scope raises ``ValueError``
+    that names the reason; ``path`` names the bytes in it."""
+    import ctypes
+
+    from . import _lib
+
+    data = bytes(data)
+    width, height = jpeg_info(data, path)[:2]
+    out = np.empty((height, width), dtype=np.uint8)
+    lib = _lib.load()
+    rc = lib.nidreg_jpeg_decode_gray(int(device), data, len(data), int(mode), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), width)
+    if rc == _lib.NIDREG_ERR_INVALID and _JPEG_REFUSAL in _lib.last_error():
+        raise _jpeg_refusal(path, _lib.last_error())
+    _lib.check(rc, "nidreg_jpeg_decode_gray")
+    return out
+
+
+def apply_exif_orientation(image, orientation):
+    """What ``cv::imread`` does with EXIF orientations 2-8 (OpenCV's ExifTransform): flips and transposes"""
+    if orientation == 2:
+        image = image[:, ::-1]
+    elif orientation == 3:
+        image = image[::-1, ::-1]
+    elif orientation == 4:
+        image = image[::-1]
+    elif orientation == 5:
+        image = image.T
+    elif orientation == 6:
+        image = image.T[:, ::-1]
+    elif orientation == 7:
+        image = image.T[::-1, ::-1]
+    elif orientation == 8:
+        image = image.T[::-1]
+    return np.ascontiguousarray(image)
+
+
+def read_image_gray(path, device=0):
+    """``cv::imread(path, 0)`` for the formats decoded here.  A PNG goes through ``read_png_gray``, unchanged.  A JPEG (by its SOI
+    marker or its file name) is decoded in LUMA mode and then turned as its EXIF orientation says: ``cv::imread`` honours the tag
+    unless ``IMREAD_UNCHANGED`` is passed."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:8] != _PNG_SIG and (data[:2] == b"\xff\xd8" or path.lower().endswith((".jpg", ".jpeg"))):
+        orientation = jpeg_info(data, path)[4]
+        return apply_exif_orientation(decode_jpeg_gray(data, JPEG_GRAY_LUMA, device=device, path=path), orientation)
+    return read_png_gray(path)
 
 
 # --------------------------------------------------------------------------------------------- calib.json

@@ -18,7 +18,10 @@ order: equalise the image (``cv::equalizeHist``), voxel-filter the map, rank-equ
   filter, which is not in the reference tree and cannot be restated;
 * ``--min_distance`` is accepted and NOT applied: the reference passes it to ``load_lidar_points`` (:93), which never uses it.  The
   integrator runs with a minimum distance of 0;
-* images are 8-bit PNGs (whatever ``dataset.read_png_gray`` reads); there is no JPEG decoder here, JPEG input is refused;
+* images are PNGs (whatever ``dataset.read_png_gray`` reads) or baseline JPEGs, read as ``cv::imread(path, 0)`` reads them (:69):
+  the Y plane of the stream, turned as its EXIF orientation says (``dataset.read_image_gray``; the inverse DCT runs on the GPU).
+  Progressive, arithmetic-coded, 12-bit and CMYK JPEGs are refused with the reason; the values are pinned against libjpeg-turbo,
+  not against OpenCV itself;
 * an empty ``--camera_distortion_coeffs`` string means no coefficients (the reference's ``std::stod("")`` throws);
 * ``--visualize`` is not offered; ``--device`` is an extension.
 """
@@ -36,7 +39,7 @@ _REQUIRED = ("map_path", "image_path", "dst_path", "camera_model", "camera_intri
 def build_parser():
     p = argparse.ArgumentParser(prog="preprocess_map", description="preprocess_map")
     p.add_argument("--map_path", help="path to input point cloud map (PCD or PLY)")
-    p.add_argument("--image_path", help="path to input image (8-bit PNG; JPEG is not decoded here)")
+    p.add_argument("--image_path", help="path to input image: PNG, or baseline JPEG read as cv::imread(path, 0) reads it (the Y plane, EXIF orientation applied)")
     p.add_argument("--dst_path", help="directory to save preprocessed data")
     p.add_argument("--camera_model", help="atan, plumb_bob, fisheye, omnidir, or equirectangular")
     p.add_argument("--camera_intrinsics", help="camera intrinsic parameters [fx,fy,cx,cy(,xi)] (don't put spaces between values!!)")
@@ -81,12 +84,7 @@ def load_lidar_points(path, voxel_resolution, device=0, log=print):
 
 
 def run(args, log=print):
-    image_path = args.image_path
-    with open(image_path, "rb") as f:
-        magic = f.read(3)
-    if magic == b"\xff\xd8\xff" or image_path.lower().endswith((".jpg", ".jpeg")):
-        raise ValueError(f"error: failed to load image {image_path}: JPEG images are not decoded here, convert it to an 8-bit PNG")
-    image = preprocess.equalize_hist(dataset.read_png_gray(image_path))  # :69-75 (written with the rest of the directory below)
+    image = preprocess.equalize_hist(dataset.read_image_gray(args.image_path, device=args.device))  # :69-75 (written with the rest of the directory below)
     intrinsics = parse_values(args.camera_intrinsics)
     distortion = parse_values(args.camera_distortion_coeffs)
 

@@ -18,7 +18,9 @@ GPU (``StaticPointCloudIntegrator.insert_cloud2``).  Differences from the refere
 * ``-d / --dynamic_lidar_integration`` is refused here with status 1 and a message: the dynamic LiDAR integration (CT-GICP) is a
   command of its own, ``preprocess_dynamic``, which runs this module's ``run`` with ``odometry.DynamicPointCloudIntegrator``;
 * ROS2 bags (sqlite3 / mcap) are not read: a file that does not start with ``#ROSBAG V2.0`` is not a bag (``valid_bag``);
-* images: ``sensor_msgs/Image`` in mono8 / bgr8 / rgb8 / bgra8 / rgba8 and PNG ``sensor_msgs/CompressedImage``; JPEG is refused;
+* images: ``sensor_msgs/Image`` in mono8 / bgr8 / rgb8 / bgra8 / rgba8 and ``sensor_msgs/CompressedImage`` with a PNG or a baseline JPEG payload.  A JPEG
+  is decoded as ``cv_bridge::toCvCopy(msg, "mono8")`` decodes it -- to BGR, then OpenCV's luma; NOT the Y plane ``preprocess_map`` takes
+  from a JPEG file -- with the inverse DCT and the colour conversion on the GPU; streams outside the decoder's scope are refused;
 * where the reference dereferences a null message -- a cloud without x / y / z or without the intensity channel, a bag without the
   image, points or camera_info topic it needs --, where ``extract_raw_points`` gives up (big-endian data, an unsupported datatype)
   and where it aborts (an invalid ``--camera_model``): a ``ValueError`` that names the topic and the bag, status 1;
@@ -55,7 +57,8 @@ def build_parser():
     p.add_argument("-d", "--dynamic_lidar_integration", action="store_true", help="create target point cloud from dynamic LiDAR data (refused here: use preprocess_dynamic)")
     p.add_argument("-i", "--intensity_channel", default="auto", help="auto or channel name")
     p.add_argument("--camera_info_topic")
-    p.add_argument("--image_topic")
+    p.add_argument("--image_topic", help="sensor_msgs/Image, or CompressedImage with a PNG or baseline JPEG payload; a JPEG is decoded as cv_bridge::toCvCopy(msg, mono8) decodes "
+                                         "it (to BGR, then luma), which is not the Y plane cv::imread(path, 0) returns")
     p.add_argument("--points_topic")
     p.add_argument("--camera_model", default="auto", help="auto, atan, plumb_bob, fisheye(=equidistant), omnidir, or equirectangular")
     p.add_argument("--camera_intrinsics", help="camera intrinsic parameters [fx,fy,cx,cy(,xi)] (don't put spaces between values!!)")
@@ -127,7 +130,7 @@ def get_intensity_channel(args, bag, points_topic):
     return channel
 
 
-def get_image(bag, image_topic):
+def get_image(bag, image_topic, device=0):
     """src/preprocess_ros1.cpp:126-139: the first ``sensor_msgs/Image`` of the topic as mono8, else the first
     ``sensor_msgs/CompressedImage``"""
     image = _first(bag, image_topic, "Image", rosbag1.decode_image)
@@ -135,13 +138,13 @@ def get_image(bag, image_topic):
         return rosbag1.to_mono8(image)
     compressed = _first(bag, image_topic, "CompressedImage", rosbag1.decode_compressed_image)
     if compressed is not None:
-        return rosbag1.compressed_to_mono8(compressed, f"of image topic '{image_topic}' in {bag.path}")
+        return rosbag1.compressed_to_mono8(compressed, f"of image topic '{image_topic}' in {bag.path}", device=device)
     raise ValueError(f"error: failed to obtain an image (image_topic='{image_topic}') from {bag.path}: the bag holds no sensor_msgs/Image or CompressedImage message on it")
 
 
 def get_camera_params(args, bag, camera_info_topic, image_topic, log=print):
     """:349-404: ``(camera_model, (width, height), intrinsics, distortion_coeffs)``"""
-    image = get_image(bag, image_topic)
+    image = get_image(bag, image_topic, device=args.device)
     size = (int(image.shape[1]), int(image.shape[0]))
     model = args.camera_model
     if model != "auto":
@@ -272,7 +275,7 @@ def run(args, log=print, warn=_warn, integrator_factory=preprocess.StaticPointCl
     for i, filename in enumerate(bag_filenames):
         log(f"start processing {filename}")
         bag = first if i == 0 else rosbag1.Bag(filename)
-        image = preprocess.equalize_hist(get_image(bag, image_topic))  # :414-419
+        image = preprocess.equalize_hist(get_image(bag, image_topic, device=args.device))  # :414-419
         integ = integrator_factory(voxel_resolution=args.voxel_resolution, min_distance=args.min_distance, device=args.device)
         try:
             inserted, rewound, nonfinite = integrate_bag(args, bag, points_topic, intensity_channel, integ, warn=warn)

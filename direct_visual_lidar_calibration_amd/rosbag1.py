@@ -305,15 +305,18 @@ def to_mono8(image):
     return ((r * 4899 + g * 9617 + b * 1868 + 8192) >> 14).astype(np.uint8)
 
 
-def compressed_to_mono8(image, where="sensor_msgs/CompressedImage"):
-    """A PNG payload through ``dataset.decode_png_gray`` (``cv::imdecode`` to gray); JPEG is refused as ``preprocess_map`` refuses it"""
+def compressed_to_mono8(image, where="sensor_msgs/CompressedImage", device=0):
+    """``cv_bridge::toCvCopy(msg, "mono8")`` of a compressed image: a PNG payload through ``dataset.decode_png_gray``; a baseline JPEG
+    payload -- what ``image_transport`` publishes on ``.../compressed`` by default -- decoded on GPU ``device`` to BGR and taken
+    through OpenCV's luma (``dataset.decode_jpeg_gray`` in BGR mode; cv_bridge passes ``IMREAD_UNCHANGED``, so no EXIF orientation
+    is applied).  A JPEG outside the decoder's scope is refused with the reason."""
     from . import dataset
 
     payload = bytes(image.data)
     if payload[:8] != dataset.PNG_SIGNATURE:
-        if payload[:3] == b"\xff\xd8\xff" or "jpeg" in image.format.lower() or "jpg" in image.format.lower():
-            raise ValueError(f"error: failed to load image {where}: JPEG images are not decoded here, convert it to an 8-bit PNG")
-        raise ValueError(f"error: failed to load image {where}: format '{image.format}' is not a PNG payload (only PNG is decoded here)")
+        if payload[:2] == b"\xff\xd8" or "jpeg" in image.format.lower() or "jpg" in image.format.lower():
+            return dataset.decode_jpeg_gray(payload, dataset.JPEG_GRAY_BGR, device=device, path=where)
+        raise ValueError(f"error: failed to load image {where}: format '{image.format}' is not a PNG or JPEG payload")
     return dataset.decode_png_gray(payload, where)
 
 

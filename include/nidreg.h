@@ -540,6 +540,56 @@ int nidreg_features_detect(int device_id, const uint8_t* image, int width, int h
 int nidreg_features_match(int device_id, const uint32_t* desc0, int n0, const uint32_t* desc1, int n1, int max_distance, int ratio_num, int ratio_den,
                           int32_t* match01_out /* n0: column or -1 */, int32_t* dist_out /* n0: best distance */, int32_t* second_out /* n0, nullable */);
 
+/* ---- baseline JPEG images to 8-bit gray ------------------------------------------------------------------------------------------
+ * The reference reads its camera image with cv::imread(image_path, 0) (src/preprocess_map.cpp:69) and, from a bag, with
+ * cv_bridge::toCvCopy(*msg, "mono8") (src/preprocess_ros1.cpp:104-134); for JPEG bytes the two give DIFFERENT gray values, and this
+ * decoder has a mode for each:
+ *   NIDREG_JPEG_GRAY_LUMA   cv::imread(path, 0): libjpeg is asked for JCS_GRAYSCALE and returns the Y plane; chroma is never decoded
+ *                           (no chroma kernel is launched).  EXIF orientation is NOT applied here (dataset.read_image_gray applies it).
+ *   NIDREG_JPEG_GRAY_BGR    cv_bridge: decode to BGR -- fancy chroma upsampling, libjpeg's YCbCr -> RGB tables --, then OpenCV's
+ *                           fixed-point luma (4899 R + 9617 G + 1868 B + 8192) >> 14.
+ * A one-component stream gives its plane in both modes.  Marker parsing and Huffman decoding run on the host
+ * (csrc/nid_jpeg_host.hpp); dequantisation, libjpeg's jpeg_idct_islow, upsampling, colour and luma are integer device kernels
+ * (csrc/nid_jpeg_kernels.hpp, which states the arithmetic).  The outputs equal tests/jpeg_oracle.py bit for bit.
+ * PINNED against libjpeg-turbo as Pillow bundles it (tests/golden/jpeg_cases.npz) plus this project's luma constants; UNPINNED
+ * against OpenCV itself, which was not available to compare with.
+ * Accepted: SOF0, and SOF1 with 8-bit samples and Huffman coding; 1 component, or 3 coded as YCbCr (libjpeg's rule: a JFIF marker or
+ * no marker at all means YCbCr, an Adobe APP14 marker must say transform 1); one interleaved scan; chroma sampled 1x1 with luma 1x1
+ * (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0); DQT with 8- or 16-bit entries; several tables per DHT / DQT segment and redefinition before
+ * SOS; DRI with RST0-7; 0xFF00 stuffing and 0xFF fill bytes before markers; APPn and COM are skipped; whatever follows the last MCU
+ * (EOI or not) is ignored.
+ * Refused with NIDREG_ERR_INVALID, nothing written and BEFORE any device call (all parsing, entropy decoding included, comes first),
+ * the message being "<function>: JPEG images are not decoded here unless they are baseline 8-bit Huffman streams (<reason>)":
+ * progressive, arithmetic-coded, lossless, hierarchical and 12-bit streams; 4 components, Adobe transform 0 (RGB) or 2 (YCCK),
+ * component identifiers R G B without a marker; a scan that holds only some of the components; every other sampling combination
+ * (4:4:0, 4:1:1, ...); a width or height of 0 or above 32768; a missing table; a Huffman table that is no prefix code.
+ * DELIBERATE DIFFERENCES from libjpeg, which decodes on with a warning in each case: entropy data that ends before the last MCU
+ * (libjpeg pads with zero bits), a Huffman code that does not exist (libjpeg substitutes 0), a zero run that carries a coefficient
+ * past position 63 (libjpeg stores it at 63) and a restart marker that is missing or out of sequence (libjpeg resynchronises) are
+ * all refused.  RANGE LIMIT: the inverse DCT saturates to [0, 255] like libjpeg-turbo's SIMD code, where libjpeg's C table wraps
+ * modulo 1024 beyond +-512; beyond the domain in which the SIMD code's int16 intermediates hold (dequantised coefficients and
+ * column-pass outputs within int16) the result is this decoder's own (int32 throughout) and pinned to nothing.
+ *   nidreg_jpeg_info          host only.  subsampling: NIDREG_JPEG_SUB_*; exif_orientation: tag 0x0112 of the first Exif APP1 segment
+ *                             (big- or little-endian TIFF header), 1 when absent or outside 1..8.  Any output may be NULL.
+ *   nidreg_jpeg_coefficients  host only: the QUANTISED blocks of one component, 64 int16 in natural (row-major) order per block, in
+ *                             raster order over the component's whole block grid -- ceil(width / (8 hmax)) * h blocks a row,
+ *                             ceil(height / (8 vmax)) * v rows --, and its quantisation table in natural order (nullable).  capacity:
+ *                             int16 values `out` holds.  The entropy stage can be checked with it on a machine without a GPU.
+ *   nidreg_jpeg_decode_gray   out: height rows of width bytes, row_stride bytes apart (0: packed); bytes between rows are not
+ *                             written.  data and out are host memory.
+ *   nidreg_jpeg_get_timing    host wall-clock milliseconds of the calling thread's last nidreg_jpeg_decode_gray: [0] parsing and
+ *                             entropy decode, [1] allocation and upload, [2] kernels (launch to idle), [3] copy back. */
+#define NIDREG_JPEG_GRAY_LUMA 0
+#define NIDREG_JPEG_GRAY_BGR 1
+#define NIDREG_JPEG_SUB_GRAY 0
+#define NIDREG_JPEG_SUB_444 1
+#define NIDREG_JPEG_SUB_422 2
+#define NIDREG_JPEG_SUB_420 3
+int nidreg_jpeg_info(const uint8_t* data, int64_t size, int32_t* width, int32_t* height, int32_t* components, int32_t* subsampling, int32_t* exif_orientation);
+int nidreg_jpeg_coefficients(const uint8_t* data, int64_t size, int component, int16_t* out, int64_t capacity, uint16_t* qtable_out /* 64, nullable */);
+int nidreg_jpeg_decode_gray(int device_id, const uint8_t* data, int64_t size, int mode, uint8_t* out, int64_t row_stride);
+int nidreg_jpeg_get_timing(double* ms4);
+
 /* ---- split-phase evaluation for a pair whose points are sharded across GPUs --------------
  * rank r:  nidreg_shard_hist(h, se3)      zero + accumulate this shard's fixed-point histogram
  *          <caller: all-reduce(sum, int64) of ext_hist over ranks, ordered on ext_stream>
