@@ -17,10 +17,8 @@ from . import odometry, preprocess_ros1
 from .preprocess_map import _attach_values
 
 
-def build_parser():
-    p = preprocess_ros1.build_parser()
-    p.prog = "preprocess_dynamic"
-    p.description = "preprocess with dynamic LiDAR integration"
+def add_dynamic_options(p):
+    """The options of the dynamic integrator that ``preprocess_ros1``'s parser does not have (``preprocess_ros2 -d`` takes them too)"""
     p.add_argument("--target_num_points", type=int, default=10000, help="points a scan is sampled down to for the registration")
     p.add_argument("--seed", type=int, default=0, help="seed of the scan sampler")
     p.add_argument("--lru_thresh", type=int, default=100, help="extension: scans after which the registration model drops a voxel it neither inserted into nor searched "
@@ -28,15 +26,26 @@ def build_parser():
     return p
 
 
-def run(args, **kw):
+def build_parser():
+    p = preprocess_ros1.build_parser()
+    p.prog = "preprocess_dynamic"
+    p.description = "preprocess with dynamic LiDAR integration"
+    return add_dynamic_options(p)
+
+
+def integrator_factory(args):
+    """The checks of the dynamic options, then the factory ``preprocess_ros1.run`` builds one integrator per bag with"""
     if args.k_neighbors < 2 or args.k_neighbors > 32:
         raise ValueError(f"error: --k_neighbors {args.k_neighbors}: 2..32 neighbours are supported")
     if args.target_num_points < args.k_neighbors:
         raise ValueError(f"error: --target_num_points {args.target_num_points} is below --k_neighbors {args.k_neighbors}")
     if args.lru_thresh < 0:
         raise ValueError(f"error: --lru_thresh {args.lru_thresh}: must be >= 0 (0 disables the eviction)")
-    factory = functools.partial(odometry.DynamicPointCloudIntegrator, k_neighbors=args.k_neighbors, target_num_points=args.target_num_points, seed=args.seed, lru_thresh=args.lru_thresh)
-    return preprocess_ros1.run(args, integrator_factory=factory, **kw)
+    return functools.partial(odometry.DynamicPointCloudIntegrator, k_neighbors=args.k_neighbors, target_num_points=args.target_num_points, seed=args.seed, lru_thresh=args.lru_thresh)
+
+
+def run(args, **kw):
+    return preprocess_ros1.run(args, integrator_factory=integrator_factory(args), **kw)
 
 
 def main(argv=None):

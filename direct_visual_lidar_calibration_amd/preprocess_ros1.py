@@ -17,7 +17,8 @@ GPU (``StaticPointCloudIntegrator.insert_cloud2``).  Differences from the refere
 
 * ``-d / --dynamic_lidar_integration`` is refused here with status 1 and a message: the dynamic LiDAR integration (CT-GICP) is a
   command of its own, ``preprocess_dynamic``, which runs this module's ``run`` with ``odometry.DynamicPointCloudIntegrator``;
-* ROS2 bags (sqlite3 / mcap) are not read: a file that does not start with ``#ROSBAG V2.0`` is not a bag (``valid_bag``);
+* ROS2 bags (sqlite3 / mcap) are not read here: a file that does not start with ``#ROSBAG V2.0`` is not a bag (``valid_bag``).  They are
+  ``preprocess_ros2``'s, which runs this module's ``run`` with ``rosbag2`` as the reader;
 * images: ``sensor_msgs/Image`` in mono8 / bgr8 / rgb8 / bgra8 / rgba8 and ``sensor_msgs/CompressedImage`` with a PNG or a baseline JPEG payload.  A JPEG
   is decoded as ``cv_bridge::toCvCopy(msg, "mono8")`` decodes it -- to BGR, then OpenCV's luma; NOT the Y plane ``preprocess_map`` takes
   from a JPEG file -- with the inverse DCT and the colour conversion on the GPU; streams outside the decoder's scope are refused;
@@ -71,10 +72,10 @@ def build_parser():
     return p
 
 
-def find_bags(data_path):
-    """:84-103: the files of ``data_path`` that open as a bag, sorted"""
+def find_bags(data_path, reader=rosbag1):
+    """:84-103: the entries of ``data_path`` that open as a bag of ``reader`` (``rosbag1``: files; ``rosbag2``: files and directories), sorted"""
     names = [os.path.join(data_path, n) for n in os.listdir(data_path)]
-    return sorted(p for p in names if os.path.isfile(p) and rosbag1.valid_bag(p))
+    return sorted(p for p in names if (os.path.isfile(p) or os.path.isdir(p)) and reader.valid_bag(p))
 
 
 def get_topics(args, bag, log=print, warn=_warn):
@@ -111,14 +112,14 @@ def _first(bag, topic, type_name, decode):
     return None if m is None else decode(m.data)
 
 
-def get_intensity_channel(args, bag, points_topic):
+def get_intensity_channel(args, bag, points_topic, reader=rosbag1):
     """:319-347: the named channel, or with ``auto`` the field of the first cloud with the highest priority: ``reflectivity`` (2)
     beats ``intensity`` (1)"""
     channel = args.intensity_channel
     if channel != "auto":
         return channel
     priorities = {"auto": -1, "intensity": 1, "reflectivity": 2}
-    cloud = _first(bag, points_topic, "PointCloud2", rosbag1.decode_pointcloud2)
+    cloud = _first(bag, points_topic, "PointCloud2", reader.decode_pointcloud2)
     if cloud is None:
         raise ValueError(f"error: no sensor_msgs/PointCloud2 message on points topic '{points_topic}' in {bag.path}")
     for f in cloud.fields:
@@ -130,21 +131,21 @@ def get_intensity_channel(args, bag, points_topic):
     return channel
 
 
-def get_image(bag, image_topic, device=0):
+def get_image(bag, image_topic, device=0, reader=rosbag1):
     """src/preprocess_ros1.cpp:126-139: the first ``sensor_msgs/Image`` of the topic as mono8, else the first
     ``sensor_msgs/CompressedImage``"""
-    image = _first(bag, image_topic, "Image", rosbag1.decode_image)
+    image = _first(bag, image_topic, "Image", reader.decode_image)
     if image is not None:
         return rosbag1.to_mono8(image)
-    compressed = _first(bag, image_topic, "CompressedImage", rosbag1.decode_compressed_image)
+    compressed = _first(bag, image_topic, "CompressedImage", reader.decode_compressed_image)
     if compressed is not None:
         return rosbag1.compressed_to_mono8(compressed, f"of image topic '{image_topic}' in {bag.path}", device=device)
     raise ValueError(f"error: failed to obtain an image (image_topic='{image_topic}') from {bag.path}: the bag holds no sensor_msgs/Image or CompressedImage message on it")
 
 
-def get_camera_params(args, bag, camera_info_topic, image_topic, log=print):
+def get_camera_params(args, bag, camera_info_topic, image_topic, log=print, reader=rosbag1):
     """:349-404: ``(camera_model, (width, height), intrinsics, distortion_coeffs)``"""
-    image = get_image(bag, image_topic, device=args.device)
+    image = get_image(bag, image_topic, device=args.device, reader=reader)
     size = (int(image.shape[1]), int(image.shape[0]))
     model = args.camera_model
     if model != "auto":
@@ -158,7 +159,7 @@ def get_camera_params(args, bag, camera_info_topic, image_topic, log=print):
             raise ValueError("error: camera_distortion_coeffs has not been set!!")
         return model, size, parse_values(args.camera_intrinsics), parse_values(args.camera_distortion_coeffs)
     log("try to get the camera model automatically")
-    info = _first(bag, camera_info_topic, "CameraInfo", rosbag1.decode_camera_info)
+    info = _first(bag, camera_info_topic, "CameraInfo", reader.decode_camera_info)
     if info is None:
         raise ValueError(f"error: no sensor_msgs/CameraInfo message on camera_info topic '{camera_info_topic}' in {bag.path} (name --camera_model and the intrinsics instead)")
     model, intrinsics, distortion = rosbag1.camera_from_info(info)
@@ -192,7 +193,7 @@ def frame_times(cloud, where):
     return stamp, first, last, lambda: float(rosbag1.read_field_all(cloud, field).min()) / scale
 
 
-def integrate_bag(args, bag, points_topic, intensity_channel, integrator, warn=_warn):
+def integrate_bag(args, bag, points_topic, intensity_channel, integrator, warn=_warn, reader=rosbag1):
     """:442-460: every PointCloud2 message of the topic, in the view's order, through the time keeper and into the integrator.
     Returns ``(frames inserted, frames skipped for a rewinding stamp, points skipped for a non-finite coordinate)``.  An integrator
     with ``insert_cloud2_timed`` (the dynamic one) also gets the frame's per-point times, as the time field and the affine map of
@@ -204,7 +205,7 @@ def integrate_bag(args, bag, points_topic, intensity_channel, integrator, warn=_
         where = f"(message {k} of points topic '{points_topic}' in {bag.path})"
         if not (m.type.endswith("/PointCloud2") or m.type == "PointCloud2"):
             break  # read_next returns nullptr at the first message that does not instantiate (src/preprocess_ros1.cpp:33-36)
-        cloud = rosbag1.decode_pointcloud2(m.data)
+        cloud = reader.decode_pointcloud2(m.data)
         names = [f.name for f in cloud.fields]
         if any(c not in names for c in ("x", "y", "z")):
             raise ValueError(f"error: missing point coordinate fields {where}: the cloud has {', '.join(names)}")
@@ -235,10 +236,12 @@ def integrate_bag(args, bag, points_topic, intensity_channel, integrator, warn=_
     return inserted, rewound, nonfinite
 
 
-def run(args, log=print, warn=_warn, integrator_factory=preprocess.StaticPointCloudIntegrator):
+def run(args, log=print, warn=_warn, integrator_factory=preprocess.StaticPointCloudIntegrator, reader=rosbag1):
+    """The steps of the module docstring; ``reader`` is the module that opens and decodes the bags: ``rosbag1``, or ``rosbag2`` for
+    ``preprocess_ros2``, which has the same surface"""
     log(f"data_path: {args.data_path}")
     log(f"dst_path : {args.dst_path}")
-    bag_filenames = find_bags(args.data_path)
+    bag_filenames = find_bags(args.data_path, reader)
     log("input_bags:")
     for f in bag_filenames:
         log(f"- {f}")
@@ -257,15 +260,15 @@ def run(args, log=print, warn=_warn, integrator_factory=preprocess.StaticPointCl
         if not bag_filenames:
             raise ValueError("error: no input bags!!")
 
-    first = rosbag1.Bag(bag_filenames[0])
+    first = reader.Bag(bag_filenames[0])
     camera_info_topic, image_topic, points_topic = get_topics(args, first, log=log, warn=warn)
     log("selected topics:")
     log(f"- camera_info: {camera_info_topic}")
     log(f"- image      : {image_topic}")
     log(f"- points     : {points_topic}")
-    intensity_channel = get_intensity_channel(args, first, points_topic)
+    intensity_channel = get_intensity_channel(args, first, points_topic, reader=reader)
     log(f"intensity_channel: {intensity_channel}")
-    camera_model, image_size, intrinsics, distortion = get_camera_params(args, first, camera_info_topic, image_topic, log=log)
+    camera_model, image_size, intrinsics, distortion = get_camera_params(args, first, camera_info_topic, image_topic, log=log, reader=reader)
     log(f"camera_model: {camera_model}")
     log(f"image_size  : {image_size[0]} {image_size[1]}")
     log(f"intrinsics  : {' '.join(f'{v:g}' for v in intrinsics)}")
@@ -274,11 +277,11 @@ def run(args, log=print, warn=_warn, integrator_factory=preprocess.StaticPointCl
     bags = []
     for i, filename in enumerate(bag_filenames):
         log(f"start processing {filename}")
-        bag = first if i == 0 else rosbag1.Bag(filename)
-        image = preprocess.equalize_hist(get_image(bag, image_topic, device=args.device))  # :414-419
+        bag = first if i == 0 else reader.Bag(filename)
+        image = preprocess.equalize_hist(get_image(bag, image_topic, device=args.device, reader=reader))  # :414-419
         integ = integrator_factory(voxel_resolution=args.voxel_resolution, min_distance=args.min_distance, device=args.device)
         try:
-            inserted, rewound, nonfinite = integrate_bag(args, bag, points_topic, intensity_channel, integ, warn=warn)
+            inserted, rewound, nonfinite = integrate_bag(args, bag, points_topic, intensity_channel, integ, warn=warn, reader=reader)
             records = integ.get_records()
         finally:
             integ.close()
