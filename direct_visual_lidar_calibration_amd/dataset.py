@@ -11,6 +11,7 @@ here                                    reference
 ``write_ply_colored``                   no counterpart: float x y z + uchar red green blue, what the headless viewer saves
 ``read_pcd``                            ``pcl::io::load`` of a PCD map into ``PointXYZI`` (PCL, not in the tree; preprocess_map.cpp:129-131)
 ``read_png_gray`` / ``write_png_gray``  ``cv::imread(path, 0)`` / ``cv::imwrite`` for 8-bit single-channel PNGs
+``write_index_png``                     ``cv::imwrite`` of the CV_8UC4 view of an int32 index image (preprocess.cpp:207-211)
 ``read_image_gray``                     ``cv::imread(path, 0)`` for a camera photograph (preprocess_map.cpp:69): PNG as above, or a baseline
                                         JPEG -- the Y plane, then the EXIF orientation -- decoded on the GPU (``decode_jpeg_gray``)
 ``decode_jpeg_gray``                    libjpeg as OpenCV drives it, in the two ways the reference does: ``cv::imread(path, 0)`` (LUMA) and
@@ -428,6 +429,15 @@ def write_png(path, image):
         f.write(_png_chunk(b"IEND", b""))
 
 
+def write_index_png(path, index):
+    """An int32 (H, W) index image in the ``_lidar_indices.png`` layout (preprocess.cpp:207-211), which ``pose.read_index_image``
+    reads back: the little-endian words as 4 bytes per pixel; cv::imwrite takes the CV_8UC4 buffer as BGRA and the PNG stores RGBA,
+    so bytes 0 and 2 swap."""
+    idx = np.asarray(index)
+    idx4 = np.ascontiguousarray(idx, dtype="<i4").view(np.uint8).reshape(idx.shape[0], idx.shape[1], 4)
+    write_png(path, idx4[:, :, [2, 1, 0, 3]])
+
+
 def write_png_gray(path, image):
     img = np.asarray(image)
     if img.ndim != 2:
@@ -623,9 +633,7 @@ def write_preprocessed(data_path, camera, bags, init_T_lidar_camera_tum=None, me
             inten, idx = lidar_images[name]
             # convertTo(CV_8UC1, 255.0): saturate_cast<uchar>(round-half-even(v * 255))
             write_png_gray(os.path.join(data_path, name + "_lidar_intensities.png"), np.clip(np.rint(np.asarray(inten) * 255.0), 0, 255).astype(np.uint8))
-            idx4 = np.ascontiguousarray(idx, dtype="<i4").view(np.uint8).reshape(idx.shape[0], idx.shape[1], 4)
-            # cv::imwrite takes the CV_8UC4 buffer as BGRA and the PNG stores RGBA: bytes 0 and 2 swap
-            write_png(os.path.join(data_path, name + "_lidar_indices.png"), idx4[:, :, [2, 1, 0, 3]])
+            write_index_png(os.path.join(data_path, name + "_lidar_indices.png"), idx)
     config = {
         "meta": dict({"data_path": data_path, "bag_names": [b[0] for b in bags]}, **(meta or {})),
         "camera": {"camera_model": camera[0], "intrinsics": [float(v) for v in camera[1]], "distortion_coeffs": [float(v) for v in camera[2]]},

@@ -130,12 +130,13 @@ def orbit_pose(T_camera_lidar, angle_deg, pivot_lidar):
     return T_view_camera @ T
 
 
-def _bag_views(args, proj, bag, label, T_lidar_camera, dst, log):
-    """The files of one bag under one transform; returns its entry of viewer.json."""
+def overlay_and_nid(args, proj, bag, T_camera_lidar):
+    """What one transform looks like on one bag's camera image, and its score: ``(overlay rgb (H, W, 3), its index image, the number
+    of points the cost sees, NID)``.  The points are those ``ViewCulling`` keeps under the transform, drawn over the grey image through
+    the camera's own model; the NID is ``CostCalculatorNID`` on the same points.  Reads ``args.disable_culling``, ``point_radius``,
+    ``alpha``, ``nid_bins`` and ``device``.  ``initial_guess_manual --candidates`` shows its 24 mountings with this too."""
     size = (bag.image.shape[1], bag.image.shape[0])
-    T_camera_lidar = np.linalg.inv(T_lidar_camera)
     points, intensities = bag.points, bag.intensities
-
     culling = nid.ViewCulling(proj, size, nid.ViewCullingParams(not args.disable_culling), device=args.device)
     keep = culling.cull(points, T_camera_lidar)
     culled, culled_int = np.ascontiguousarray(points[keep]), np.ascontiguousarray(intensities[keep])
@@ -144,13 +145,21 @@ def _bag_views(args, proj, bag, label, T_lidar_camera, dst, log):
     r.set_colors(render.quantize_colors(render.colormap_turbo(culled_int)))
     overlay, index = r.draw(proj, size, T_camera_lidar, radius=args.point_radius, background=grey, alpha=args.alpha)
     r.close()
-    dataset.write_png(os.path.join(dst, f"{bag.bag_name}_{label}_overlay.png"), overlay)
 
     value = float("nan")  # (no point survives: there is nothing to score)
     if len(keep):
         cost = nid.CostCalculatorNID(proj, bag.image, culled, culled_int, nid.NIDCostParams(args.nid_bins), device=args.device)
         value = cost.calculate(T_camera_lidar)
         cost.close()
+    return overlay, index, len(keep), value
+
+
+def _bag_views(args, proj, bag, label, T_lidar_camera, dst, log):
+    """The files of one bag under one transform; returns its entry of viewer.json."""
+    T_camera_lidar = np.linalg.inv(T_lidar_camera)
+    points, intensities = bag.points, bag.intensities
+    overlay, index, num_culled, value = overlay_and_nid(args, proj, bag, T_camera_lidar)
+    dataset.write_png(os.path.join(dst, f"{bag.bag_name}_{label}_overlay.png"), overlay)
 
     updater = render.PointsColorUpdater(proj, bag.image, points, intensities, device=args.device)
     colors = render.quantize_colors(updater.update(T_camera_lidar, args.blend_weight))
@@ -166,7 +175,7 @@ def _bag_views(args, proj, bag, label, T_lidar_camera, dst, log):
     r.close()
     if args.save_ply:
         dataset.write_ply_colored(os.path.join(dst, f"{bag.bag_name}_{label}_colored.ply"), points, colors[:, :3])
-    entry = {"points": int(len(points)), "culled": int(len(keep)), "colored": int(seen.sum()), "overlay_pixels_covered": int((index >= 0).sum()), "nid": float(value)}
+    entry = {"points": int(len(points)), "culled": int(num_culled), "colored": int(seen.sum()), "overlay_pixels_covered": int((index >= 0).sum()), "nid": float(value)}
     log(f"{bag.bag_name} [{label}]: {entry['points']} points, {entry['culled']} after culling, {entry['overlay_pixels_covered']} overlay pixels, NID {value:.6f}")
     return entry
 
