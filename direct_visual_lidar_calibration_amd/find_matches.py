@@ -3,6 +3,7 @@ intensity image and the matches between them, written to ``<bag>_matches.json`` 
 
     python -m direct_visual_lidar_calibration_amd.find_matches <data_path> [--max_keypoints 2048] [--nms_radius 4]
         [--fast_threshold T] [--max_distance D] [--ratio R] [--levels 8] [--rotate_camera 0] [--rotate_lidar 0] [--device 0]
+        [--picture | --picture_only]
 
 This takes the place of the reference's ``scripts/find_matches_superglue.py`` and is NOT a port of it: SuperGlue needs pretrained
 weights under a non-commercial licence, and OpenCV.  What runs here is a classical stand-in (matching.py: FAST-9 over a 6/5 pyramid,
@@ -10,7 +11,13 @@ upright BRIEF-256, mutual-best Hamming matching with a ratio test; integer arith
 keeps the command line's shape (``data_path``, ``--max_keypoints``, ``--nms_radius``, ``--rotate_camera``, ``--rotate_lidar``) and the
 four JSON keys.  Its quality on real camera / LiDAR pairs is unmeasured.  Two deliberate differences: ``--max_keypoints`` defaults to
 2048 (the reference: -1), and a rotation is undone exactly -- for 90 degrees clockwise the original pixel is (y_r, H - 1 - x_r), where
-the reference script computes H - x_r, one pixel off.  The match visualisation image (``<bag>_superglue.png``) is not built.
+the reference script computes H - x_r, one pixel off.
+
+``--picture`` also writes the match visualisation image, the reference script's ``<bag>_superglue.png``, as ``<bag>_matches.png``: both
+images side by side, every keypoint circled, every match a line coloured by its confidence (draw.py says how it differs from the
+script's: unrotated images, RGB colours, an integer resize).  ``--picture_only`` draws it from the ``<bag>_matches.json`` files already
+in the directory and runs no detection or matching; it draws a file the reference's SuperGlue script wrote just as well (float
+keypoints are truncated; a keypoint outside its image is refused).  ``--show_keypoints``, which opens a window, is not built.
 """
 import argparse
 import json
@@ -19,7 +26,7 @@ import sys
 
 import numpy as np
 
-from . import dataset, matching, pose
+from . import dataset, draw, matching, pose
 
 
 def build_parser():
@@ -35,15 +42,38 @@ def build_parser():
     p.add_argument("--rotate_camera", type=int, default=0, choices=(0, 90, 180, 270), help="rotate camera image before matching (CW)")
     p.add_argument("--rotate_lidar", type=int, default=0, choices=(0, 90, 180, 270), help="rotate LiDAR image before matching (CW)")
     p.add_argument("--device", type=int, default=0, help="GPU")
+    g = p.add_mutually_exclusive_group()
+    g.add_argument("--picture", action="store_true", help="also write <bag>_matches.png: both images, keypoints and matches")
+    g.add_argument("--picture_only", action="store_true", help="draw <bag>_matches.png from the <bag>_matches.json already there; no detection or matching")
     return p
 
 
+def write_picture(data_path, bag_name, camera, lidar, result, device=0):
+    """``<bag>_matches.png`` of one bag (draw.match_picture); returns its path"""
+    path = os.path.join(data_path, bag_name + "_matches.png")
+    dataset.write_png(path, draw.match_picture(camera, lidar, result, device=device))
+    return path
+
+
 def run(args, log=print):
+    """Returns the ``<bag>_matches.json`` paths written (none with ``--picture_only``); the pictures are named in the log only."""
     config = dataset.read_calib(args.data_path)
     written = []
     for bag_name in config["meta"]["bag_names"]:
         camera = dataset.read_png_gray(os.path.join(args.data_path, bag_name + ".png"))
         lidar = dataset.read_png_gray(os.path.join(args.data_path, bag_name + "_lidar_intensities.png"))
+        if args.picture_only:
+            path = os.path.join(args.data_path, bag_name + "_matches.json")
+            if not os.path.exists(path):
+                raise FileNotFoundError(f"error: failed to open {path}")
+            with open(path) as f:
+                result = json.load(f)
+            try:
+                picture = write_picture(args.data_path, bag_name, camera, lidar, result, device=args.device)
+            except ValueError as e:
+                raise ValueError(f"{path}: {e}") from None
+            log(f"{bag_name}: {sum(1 for m in result['matches'] if m >= 0)} matches of {path} -> {picture}")
+            continue
         indices = pose.read_index_image(os.path.join(args.data_path, bag_name + "_lidar_indices.png"))
         if indices.shape != lidar.shape:
             raise ValueError(f"{bag_name}: the LiDAR index image is {indices.shape[1]}x{indices.shape[0]}, the intensity image {lidar.shape[1]}x{lidar.shape[0]}")
@@ -54,7 +84,8 @@ def run(args, log=print):
         with open(path, "w") as f:
             json.dump(result, f)
         n = sum(1 for m in result["matches"] if m >= 0)
-        log(f"{bag_name}: {len(result['kpts0']) // 2} camera keypoints, {len(result['kpts1']) // 2} LiDAR keypoints, {n} matches -> {path}")
+        picture = ", " + write_picture(args.data_path, bag_name, camera, lidar, result, device=args.device) if args.picture else ""
+        log(f"{bag_name}: {len(result['kpts0']) // 2} camera keypoints, {len(result['kpts1']) // 2} LiDAR keypoints, {n} matches -> {path}{picture}")
         written.append(path)
     return written
 

@@ -590,6 +590,37 @@ int nidreg_jpeg_coefficients(const uint8_t* data, int64_t size, int component, i
 int nidreg_jpeg_decode_gray(int device_id, const uint8_t* data, int64_t size, int mode, uint8_t* out, int64_t row_stride);
 int nidreg_jpeg_get_timing(double* ms4);
 
+/* ---- match pictures: a 2-D primitive rasteriser (csrc/nid_draw_kernels.hpp; Python: draw.py) ------------------------------------
+ * What find_matches --picture and initial_guess_auto --picture draw with, in place of the reference script's OpenCV calls
+ * (scripts/find_matches_superglue.py: both images side by side, keypoints circled, matches as lines).  Stateless; all pointers are
+ * host memory; integer arithmetic only on the device, so the picture is the same on every run and restated byte for byte in
+ * tests/draw_oracle.py.
+ * CANVAS  out_rgb: left_h rows of canvas_w pixels of 3 bytes (R, G, B), packed.  canvas_w = left_w when right_gray is NULL (right_w,
+ * right_h and right_row_stride are then ignored), else 2 * left_w.  Left panel: the gray value in all three channels.  Right panel:
+ * the right image resized to left_w x left_h by exact integer bilinear interpolation with pixel-centre alignment -- per axis, for
+ * destination index i and sizes n_d (destination) and n_s (source): num = (2 i + 1) n_s - n_d, den = 2 n_d, i0 = floor(num / den),
+ * f = num - i0 den, the taps i0 (weight den - f) and i0 + 1 (weight f) clamped to [0, n_s - 1]; the value is
+ * (sum of taps x weights + den_x den_y / 2) / (den_x den_y), floored, in 64-bit integers.  Equal sizes give the identity.
+ * PRIMITIVES  8 int32 each: {kind, x0, y0, a, b, rgb (0xRRGGBB), reserved, reserved}; the reserved words are ignored.  Coordinates
+ * are relative to the whole canvas (a caller that draws on the right panel adds left_w itself).  A pixel outside the canvas is
+ * dropped on its own, not the primitive with it.
+ *   NIDREG_DRAW_LINE  from (x0, y0) to (a, b): n = max(|dx|, |dy|); for k = 0..n the pixel
+ *                     (x0 + sgn(dx) ((2 k |dx| + n) / (2 n)), y0 + sgn(dy) ((2 k |dy| + n) / (2 n))), divisions floored; n = 0 is the one
+ *                     pixel.  Every k stands on its own and the line is defined FROM its first point: the reversed line may cover
+ *                     other pixels.  Not symmetrised, not anti-aliased, one pixel wide.
+ *   NIDREG_DRAW_RING  centre (x0, y0), radius a (b is ignored): with d2 = dx^2 + dy^2 the pixels of 4 d2 < (2 a + 1)^2 and
+ *                     (a == 0 or 4 d2 >= (2 a - 1)^2) -- 1, 8, 12, 16 pixels at radius 0, 1, 2, 3.
+ *   NIDREG_DRAW_DISC  4 d2 < (2 a + 1)^2.
+ * ORDER  the painter's rule: where several primitives cover a pixel, the one with the LARGEST index in prims wins, on every run.
+ * Refused with NIDREG_ERR_INVALID and a message, before the device is touched and with nothing written: a NULL left_gray or
+ * out_rgb, or NULL prims with num_prims > 0; a width or height outside [1, 16384]; a row stride below the width; num_prims outside
+ * [0, 2^24]; an unknown kind; a coordinate outside [-32768, 32767]; a radius outside [0, 16]; rgb above 0xFFFFFF. */
+#define NIDREG_DRAW_LINE 0
+#define NIDREG_DRAW_RING 1
+#define NIDREG_DRAW_DISC 2
+int nidreg_draw(int device_id, const uint8_t* left_gray, int left_w, int left_h, int64_t left_row_stride, const uint8_t* right_gray /* nullable */, int right_w, int right_h,
+                int64_t right_row_stride, int64_t num_prims, const int32_t* prims /* 8 int32 per primitive */, uint8_t* out_rgb /* left_h x canvas_w x 3 */);
+
 /* ---- split-phase evaluation for a pair whose points are sharded across GPUs --------------
  * rank r:  nidreg_shard_hist(h, se3)      zero + accumulate this shard's fixed-point histogram
  *          <caller: all-reduce(sum, int64) of ext_hist over ranks, ordered on ext_stream>
