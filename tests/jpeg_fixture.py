@@ -67,6 +67,7 @@ def _block_symbols(blk, pred):
     z = [int(v) for v in np.asarray(blk).reshape(64)[ZIGZAG]]
     diff = z[0] - pred
     t = _category(diff)
+    assert t <= 15, f"a DC difference of {diff} needs category {t}: decoders refuse it (give the DC values unwrapped, in a wide integer type)"
     out = [("dc", t, diff if diff >= 0 else diff + (1 << t) - 1, t)]
     run = 0
     last = max([i for i in range(1, 64) if z[i]], default=0)

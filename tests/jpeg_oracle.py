@@ -198,7 +198,7 @@ def coefficients(data):
                     blk = blocks[ci][my * c["v"] + by, mx * c["h"] + bx]
                     t = br.symbol(dc)
                     pred[ci] += _extend(br.take(t), t)
-                    blk[0] = pred[ci]
+                    blk[0] = (pred[ci] + 32768) % 65536 - 32768  # the store reduces to int16, as libjpeg's (JCOEF) cast does
                     i = 1
                     while i < 64:
                         rs = br.symbol(ac)
