@@ -81,6 +81,7 @@ EXPORTS = [
     "nidreg_features_detect", "nidreg_features_match",
     "nidreg_splat_create", "nidreg_splat_set_colors", "nidreg_splat_draw", "nidreg_splat_destroy",
     "nidreg_jpeg_info", "nidreg_jpeg_coefficients", "nidreg_jpeg_decode_gray", "nidreg_jpeg_get_timing",
+    "nidreg_image_to_mono8", "nidreg_image_get_timing",
     "nidreg_draw",
 ]
 
@@ -190,6 +191,9 @@ def load():
     lib.nidreg_jpeg_coefficients.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int16), ctypes.c_int64, ctypes.POINTER(ctypes.c_uint16)]
     lib.nidreg_jpeg_decode_gray.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_int64, ctypes.c_int, c_uint8_p, ctypes.c_int64]
     lib.nidreg_jpeg_get_timing.argtypes = [c_double_p]
+    # data as an address: the bytes may be a read-only view into a mapped bag file
+    lib.nidreg_image_to_mono8.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_char_p, ctypes.c_int, c_uint8_p, ctypes.c_int64]
+    lib.nidreg_image_get_timing.argtypes = [c_double_p]
     lib.nidreg_draw.argtypes = [ctypes.c_int, c_uint8_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_uint8_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, c_int32_p, c_uint8_p]
     lib.nidreg_rccl_unique_id.argtypes = [ctypes.c_char_p]
     lib.nidreg_shard_comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]

@@ -19,7 +19,9 @@ GPU (``StaticPointCloudIntegrator.insert_cloud2``).  Differences from the refere
   command of its own, ``preprocess_dynamic``, which runs this module's ``run`` with ``odometry.DynamicPointCloudIntegrator``;
 * ROS2 bags (sqlite3 / mcap) are not read here: a file that does not start with ``#ROSBAG V2.0`` is not a bag (``valid_bag``).  They are
   ``preprocess_ros2``'s, which runs this module's ``run`` with ``rosbag2`` as the reader;
-* images: ``sensor_msgs/Image`` in mono8 / bgr8 / rgb8 / bgra8 / rgba8 and ``sensor_msgs/CompressedImage`` with a PNG or a baseline JPEG payload.  A JPEG
+* images: ``sensor_msgs/Image`` in mono8 / bgr8 / rgb8 / bgra8 / rgba8 and, converted on the GPU (``rosbag1.image_to_mono8``; the rules are unpinned
+  against OpenCV and cv_bridge), the Bayer mosaics, yuv422 / yuv422_yuy2, mono16 and 16-bit colour; every other encoding (8UC1, 16UC1, 32FC1, nv21 ...) and a
+  mosaic below 3 x 3 are refused by name; ``sensor_msgs/CompressedImage`` with a PNG or a baseline JPEG payload.  A JPEG
   is decoded as ``cv_bridge::toCvCopy(msg, "mono8")`` decodes it -- to BGR, then OpenCV's luma; NOT the Y plane ``preprocess_map`` takes
   from a JPEG file -- with the inverse DCT and the colour conversion on the GPU; streams outside the decoder's scope are refused;
 * where the reference dereferences a null message -- a cloud without x / y / z or without the intensity channel, a bag without the
@@ -132,11 +134,11 @@ def get_intensity_channel(args, bag, points_topic, reader=rosbag1):
 
 
 def get_image(bag, image_topic, device=0, reader=rosbag1):
-    """src/preprocess_ros1.cpp:126-139: the first ``sensor_msgs/Image`` of the topic as mono8, else the first
-    ``sensor_msgs/CompressedImage``"""
+    """src/preprocess_ros1.cpp:126-139: the first ``sensor_msgs/Image`` of the topic as mono8 (``rosbag1.image_to_mono8``: Bayer, packed
+    YUV 4:2:2 and 16-bit images are converted on GPU ``device``), else the first ``sensor_msgs/CompressedImage``"""
     image = _first(bag, image_topic, "Image", reader.decode_image)
     if image is not None:
-        return rosbag1.to_mono8(image)
+        return rosbag1.image_to_mono8(image, device=device, where=f"image topic '{image_topic}' in {bag.path}")
     compressed = _first(bag, image_topic, "CompressedImage", reader.decode_compressed_image)
     if compressed is not None:
         return rosbag1.compressed_to_mono8(compressed, f"of image topic '{image_topic}' in {bag.path}", device=device)

@@ -7,7 +7,7 @@ here                                            reference (through rosbag / cv_b
 ``topics_and_types(path)``                      ``rosbag::View::getConnections`` (:79-89)
 ``Bag(path).messages(topic)``                   ``rosbag::View(bag, rosbag::TopicQuery(topic))`` (:21-26, :54-63)
 ``decode_pointcloud2 / _image / _compressed_image / _camera_info``   ``m.instantiate<sensor_msgs::...>()``
-``to_mono8`` / ``compressed_to_mono8``          ``cv_bridge::toCvCopy(msg, "mono8")`` (:126-135)
+``to_mono8`` / ``image_to_mono8`` / ``compressed_to_mono8``   ``cv_bridge::toCvCopy(msg, "mono8")`` (:126-135)
 ==============================================  =========================================================
 
 The file format (the public "Bag format 2.0" specification): the line ``#ROSBAG V2.0``, then records ``u32 header_len, header,
@@ -303,6 +303,31 @@ def to_mono8(image):
     px = rows.reshape(h, w, ch)
     r, g, b = (px[:, :, k].astype(np.int64) for k in _COLOR_ORDER[enc])
     return ((r * 4899 + g * 9617 + b * 1868 + 8192) >> 14).astype(np.uint8)
+
+
+def image_to_mono8(image, device=0, where="sensor_msgs/Image"):
+    """``cv_bridge::toCvCopy(image, "mono8")`` for every encoding converted here.  The five 8-bit encodings are ``to_mono8``'s, on the
+    host, with the bytes they always had.  Bayer mosaics (``bayer_rggb8`` ... ``bayer_grbg16``), packed YUV 4:2:2 (``yuv422`` /
+    ``uyvy``, ``yuv422_yuy2`` / ``yuyv``), ``mono16`` and ``rgb16`` / ``bgr16`` / ``rgba16`` / ``bgra16`` are converted on GPU
+    ``device`` (``nidreg_image_to_mono8``, which states the rules; unpinned against OpenCV and cv_bridge) from a zero-copy view of
+    ``image.data``, wherever it lies.  Everything else -- ``8UC1``, ``16UC1``, ``32FC1``, ``nv21`` ... -- and an image whose size,
+    step or data length is out of range raises ``ValueError`` before the device is touched; ``where`` names the message in it."""
+    import ctypes
+
+    from . import _lib
+
+    if image.encoding == "mono8" or image.encoding in _COLOR_ORDER:
+        return to_mono8(image)
+    h, w = int(image.height), int(image.width)
+    data = np.frombuffer(image.data, dtype=np.uint8)
+    out = np.empty((min(h, 16384), min(w, 16384)), dtype=np.uint8)  # (a size beyond the library's range is refused by it below)
+    lib = _lib.load()
+    rc = lib.nidreg_image_to_mono8(int(device), data.ctypes.data, data.size, w, h, int(image.step), image.encoding.encode(), int(image.is_bigendian),
+                                   out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), w)
+    if rc == _lib.NIDREG_ERR_INVALID:
+        raise ValueError(f"{where}: {_lib.last_error()}")
+    _lib.check(rc, "nidreg_image_to_mono8")
+    return out
 
 
 def compressed_to_mono8(image, where="sensor_msgs/CompressedImage", device=0):

@@ -45,8 +45,8 @@ import zlib
 import numpy as np
 
 from .rosbag1 import (DATATYPE_DTYPES, FLOAT32, FLOAT64, INT8, INT16, INT32, UINT8, UINT16, UINT32,  # noqa: F401 (the shared surface)
-                      CameraInfo, CompressedImage, Image, Message, PointCloud2, PointField, camera_from_info, compressed_to_mono8, field_table, num_points, read_field,
-                      read_field_all, stamp_to_sec, to_mono8)
+                      CameraInfo, CompressedImage, Image, Message, PointCloud2, PointField, camera_from_info, compressed_to_mono8, field_table, image_to_mono8, num_points,
+                      read_field, read_field_all, stamp_to_sec, to_mono8)
 
 SQLITE_MAGIC = b"SQLite format 3\x00"
 MCAP_MAGIC = b"\x89MCAP0\r\n"

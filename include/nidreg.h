@@ -590,6 +590,43 @@ int nidreg_jpeg_coefficients(const uint8_t* data, int64_t size, int component, i
 int nidreg_jpeg_decode_gray(int device_id, const uint8_t* data, int64_t size, int mode, uint8_t* out, int64_t row_stride);
 int nidreg_jpeg_get_timing(double* ms4);
 
+/* ---- raw sensor_msgs/Image encodings to 8-bit gray (csrc/nid_raw_kernels.hpp; Python: rosbag1.image_to_mono8) ---------------------
+ * What cv_bridge::toCvCopy(msg, "mono8") (src/preprocess_ros1.cpp:126-135) makes of an uncompressed image: besides the five 8-bit
+ * encodings, the Bayer mosaics, packed YUV 4:2:2 and the 16-bit images machine-vision cameras publish on image_raw.  Stateless; data
+ * and out are host memory; integer arithmetic only on the device (unsigned 32-bit), one launch, no atomics: the same bytes on every
+ * run, restated byte for byte in tests/raw_image_oracle.py.  The rules below restate cv_bridge and OpenCV (the bilinear Bayer2Gray,
+ * channel extraction for packed YUV, convertTo for the depth change) from memory: the result is UNPINNED against OpenCV and
+ * cv_bridge, neither of which was available to compare with.
+ * SOURCE  data: the message's bytes as stored, height rows of step bytes (size of them at least height * step); step may be odd and
+ * data may lie at any address.  luma(R, G, B) = (4899 R + 9617 G + 1868 B + 8192) >> 14.
+ * DEPTH CHANGE  every 16-bit encoding ends with (v + 128) / 257, floored: cv_bridge's convertTo(CV_8U, 255 / 65535) in float32 with
+ * round-half-even, for all 65536 values.  With is_bigendian != 0 every 16-bit sample is byte-swapped first; 8-bit encodings ignore it.
+ *   mono8, mono16                     the sample (mono16: the depth change alone)
+ *   rgb8 bgr8 rgba8 bgra8             luma; alpha is ignored (the bytes rosbag1.to_mono8 gives)
+ *   rgb16 bgr16 rgba16 bgra16         luma on the 16-bit samples, then the depth change
+ *   yuv422, uyvy                      two bytes a pixel: byte 2x + 1 of the row, the stored Y without range scaling
+ *   yuv422_yuy2, yuyv                 byte 2x; any width
+ *   bayer_{rggb,bggr,gbrg,grbg}{8,16} the four letters are the colours of row 0 (columns 0, 1), then row 1 (columns 0, 1) of the
+ *                                     mosaic p.  Interior pixel (1 <= x <= W - 2, 1 <= y <= H - 2), c_r, c_g, c_b = 4899, 9617, 1868:
+ *       at a red or blue pixel of colour C (O the other of the two)
+ *           (c_C 4p + c_g (left + right + up + down) + c_O (sum of the four diagonal neighbours) + 2^15) >> 16
+ *       at a green pixel whose horizontal neighbours have colour Ch and whose vertical neighbours have colour Cv
+ *           (c_Ch (left + right) + c_Cv (up + down) + c_g 2p + 2^14) >> 15
+ *     -- the bilinear demosaic and the luma with ONE rounding.  A border pixel takes the value of the interior pixel at
+ *     (clamp(x, 1, W - 2), clamp(y, 1, H - 2)), the pattern's phase being that of the clamped coordinate: row 0 repeats row 1, a
+ *     corner its diagonal neighbour.  The 16-bit mosaics: the same on 16-bit samples, then the depth change.
+ * Refused with NIDREG_ERR_INVALID, nothing written and BEFORE any device call: every other encoding -- 8UC1, 16UC1, 32FC1, nv21,
+ * nv24, ...; cv_bridge refuses the generic types for this target too --, the message being "nidreg_image_to_mono8: sensor_msgs/Image
+ * encoding '<enc>' is not converted here (<the list> are)"; a width or height outside [1, 16384]; a mosaic with W < 3 or H < 3 (no
+ * interior: a DELIBERATE DIFFERENCE); a step below W * bytes per pixel; size below height * step; a NULL pointer; an out_row_stride
+ * below the width (0 means packed).
+ *   nidreg_image_to_mono8    out: height rows of width bytes, out_row_stride bytes apart; bytes between rows are not written.
+ *   nidreg_image_get_timing  host wall-clock milliseconds of the calling thread's last nidreg_image_to_mono8: [0] allocation and
+ *                            upload, [1] the kernel (launch to idle), [2] copy back. */
+int nidreg_image_to_mono8(int device_id, const uint8_t* data, int64_t size, int width, int height, int64_t step, const char* encoding, int is_bigendian, uint8_t* out,
+                          int64_t out_row_stride);
+int nidreg_image_get_timing(double* ms3);
+
 /* ---- match pictures: a 2-D primitive rasteriser (csrc/nid_draw_kernels.hpp; Python: draw.py) ------------------------------------
  * What find_matches --picture and initial_guess_auto --picture draw with, in place of the reference script's OpenCV calls
  * (scripts/find_matches_superglue.py: both images side by side, keypoints circled, matches as lines).  Stateless; all pointers are
