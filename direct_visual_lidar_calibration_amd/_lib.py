@@ -17,6 +17,7 @@ NIDREG_ERR_INVALID = -1
 NIDREG_ERR_FULL = -4
 NIDREG_OUT_DOUBLES = 16
 FEATURES_CAPACITY = 65536  # NIDREG_FEATURES_CAPACITY
+SELECT_TILE = 1024  # NIDREG_SELECT_TILE
 
 MODE_SPLINE, MODE_NEAREST = 0, 1
 PREC_FP64 = 0  # (1 = NIDREG_PREC_FP32: removed in round 5, refused by nidreg_create)
@@ -83,6 +84,7 @@ EXPORTS = [
     "nidreg_jpeg_info", "nidreg_jpeg_coefficients", "nidreg_jpeg_decode_gray", "nidreg_jpeg_get_timing",
     "nidreg_image_to_mono8", "nidreg_image_get_timing",
     "nidreg_draw",
+    "nidreg_mask_create", "nidreg_mask_get", "nidreg_mask_destroy", "nidreg_cloud_select", "nidreg_cloud_select_counts", "nidreg_cloud_size", "nidreg_cloud_get",
 ]
 
 _lib = None
@@ -195,6 +197,15 @@ def load():
     lib.nidreg_image_to_mono8.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_char_p, ctypes.c_int, c_uint8_p, ctypes.c_int64]
     lib.nidreg_image_get_timing.argtypes = [c_double_p]
     lib.nidreg_draw.argtypes = [ctypes.c_int, c_uint8_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_uint8_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, c_int32_p, c_uint8_p]
+    lib.nidreg_mask_create.argtypes = [ctypes.c_int, c_uint8_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
+    lib.nidreg_mask_get.argtypes = [ctypes.c_void_p, c_uint8_p, ctypes.c_int64]
+    lib.nidreg_mask_destroy.restype = None
+    lib.nidreg_mask_destroy.argtypes = [ctypes.c_void_p]
+    lib.nidreg_cloud_select.argtypes = [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_double,
+                                        ctypes.c_double, ctypes.POINTER(ctypes.c_void_p), c_int32_p, c_int64_p]
+    lib.nidreg_cloud_size.argtypes = [ctypes.c_void_p, c_int64_p]
+    lib.nidreg_cloud_get.argtypes = [ctypes.c_void_p, c_double_p, c_double_p]
+    lib.nidreg_cloud_select_counts.argtypes = [ctypes.c_void_p, c_int64_p]
     lib.nidreg_rccl_unique_id.argtypes = [ctypes.c_char_p]
     lib.nidreg_shard_comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]
     lib.nidreg_shard_attach_rccl.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
@@ -209,7 +220,7 @@ def kernel_source_hash():
     import hashlib
 
     h = hashlib.sha256()
-    names = ["nid_device.hpp", "nid_atan_table.hpp", "nid_log_table.hpp", "nid_multi.hpp", "nid_kernels.hpp", "nid_fused.hpp", "nid_launch_impl.hpp", "nid_kernels_f64.hip", "nid_kernels_f64_exact.hip", "nid_kernels_fused.hip", "Makefile"]
+    names = ["nid_device.hpp", "nid_atan_table.hpp", "nid_log_table.hpp", "nid_multi.hpp", "nid_kernels.hpp", "nid_fused.hpp", "nid_launch_impl.hpp", "nid_kernels_f64.hip", "nid_kernels_f64_exact.hip", "nid_kernels_fused.hip", "nid_select_kernels.hpp", "nidreg_select.hip", "Makefile"]
     for path in [os.path.join(CSRC_DIR, n) for n in names]:
         h.update(os.path.basename(path).encode())
         with open(path, "rb") as f:

@@ -6,12 +6,17 @@ Mirrors the reference executable (src/calibrate.cpp:27-200) without its viewer:
     python -m direct_visual_lidar_calibration_amd.calibrate <data_path> [--nid_bins 16]
         [--registration_type nid_bfgs|nid_nelder_mead] [--disable_culling] [--first_n_bags N]
         [--nelder_mead_init_step 1e-3] [--nelder_mead_convergence_criteria 1e-8] [--auto_quit] [--background]
+        [--mask PATH|auto] [--mask_margin 2] [--min_range 0] [--max_range inf]
 
 Same option names, defaults and ``calib.json`` keys.  The per-outer-iteration work (view culling ->
 new cost object, visual_camera_calibration.cpp:76-85 / :201-206) and every cost evaluation run on the
 GPU from device-resident clouds; pairs are spread over the visible GPUs (pair k -> device k mod P), the
 plain sum of ``MultiNIDCost`` happening on the host.  The optimisers (BFGS / Nelder-Mead) stay on the
 host like the reference's Ceres / dfo.
+
+``--mask`` / ``--mask_margin`` / ``--min_range`` / ``--max_range`` (extensions) leave image regions and LiDAR ranges out of the cost:
+every outer iteration then selects its points on the device (``nid.Cloud.select``: cull, eroded mask at the point's pixel, range
+gate, stream compaction) and builds the cost object from the selected cloud.  With none of them the path is the fused one above.
 """
 import argparse
 import math
@@ -35,6 +40,7 @@ def build_parser():
     p.add_argument("--auto_quit", action="store_true", help="accepted for compatibility (there is no viewer to keep open)")
     p.add_argument("--background", action="store_true", help="accepted for compatibility (there is no viewer to hide)")
     p.add_argument("--precision", default="fp64", choices=["fp64"], help="geometry precision of the cost kernels (extension; the reference is fp64)")
+    dataset.add_selection_options(p)
     p.add_argument("--dry_run", action="store_true", help="load and validate the dataset, do not optimise or write (extension)")
     return p
 
@@ -60,13 +66,17 @@ def _upload(points, intensities, device):
     return nid.Cloud(points, intensities, device=device)
 
 
-def calibrate_pairs(proj, pairs, init_x, params, precision="fp64", stats=None):
+def calibrate_pairs(proj, pairs, init_x, params, precision="fp64", stats=None, selection=None, log=None):
     """The in-memory body of the command: ``pairs`` = [(image_u8 (H, W), points (N, 4), intensities (N,)), ...] as
     ``VisualLiDARData`` holds them -- or (image_u8, xyz float32 (N, 3), intensities float32 (N,)) as the file stores them, uploaded
     without a host widening pass -- ``init_x`` the Sophus-order ``T_camera_lidar`` 7-vector.  One upload per pair; every outer
     iteration culls + rebuilds its cost object on the device (visual_camera_calibration.cpp:76-85 / :201-206); every cost
     evaluation runs on the GPU.  Returns ``(x, VisualCameraCalibration)``; ``stats`` (optional dict) receives the wall-clock
-    split: ``upload_s`` (clouds to HBM), ``build_s`` (culling + record build of every outer iteration), ``evaluations``."""
+    split: ``upload_s`` (clouds to HBM), ``build_s`` (culling + record build of every outer iteration), ``evaluations``.
+    ``selection`` (optional): ``{"masks": [mask_u8 (H, W) | None per pair], "margin", "min_range", "max_range"}`` -- every outer
+    iteration then takes its points from ``Cloud.select`` (cull, eroded mask, range gate) and builds the cost object from the selected
+    cloud with ``cull=None``; ``log`` receives one line per pair and outer iteration with what the cull kept and what the mask and the
+    range removed."""
     ndev = _lib.load().nidreg_device_count()
     if ndev <= 0:
         raise SystemExit("error: no MI355X / HIP device visible (the NID core has no CPU fallback)")
@@ -92,11 +102,45 @@ def calibrate_pairs(proj, pairs, init_x, params, precision="fp64", stats=None):
         build_s[0] += time.perf_counter() - t1
         return c
 
+    masks = []
+    if selection is not None:
+        # the select route: sub = clouds[k].select(...) -> from_cloud(..., sub, cull=None) -> sub.close().  scale_points keeps the
+        # fixed-point unit of the whole cloud, as the fused route has it.
+        masks = [None if m is None else nid.Mask(m, margin=selection["margin"], device=k % ndev) for k, m in enumerate(selection["masks"])]
+
+        def selected(k, T):
+            sub = clouds[k].select(proj, size, T, min_z, depth, mask=masks[k], min_range=selection["min_range"], max_range=selection["max_range"])
+            if log is not None:
+                c = sub.select_counts
+                log(f"select pair {k}: the cull kept {c['culled_kept']} of {clouds[k].num_points} points, the mask removed {c['mask_removed']}, the range {c['range_removed']}: "
+                    f"{sub.num_points} points")
+            return sub
+
+        def selected_nid(k, T, bins):
+            t1 = time.perf_counter()
+            sub = selected(k, T)
+            c = nid.NIDCost.from_cloud(proj, images_f64[k], sub, bins, cull=None, precision=precision, scale_points=clouds[k].num_points)
+            sub.close()
+            build_s[0] += time.perf_counter() - t1
+            return c
+
+        def selected_nearest(k, T, bins):
+            t1 = time.perf_counter()
+            sub = selected(k, T)
+            c = nid.CostCalculatorNID.from_cloud(proj, pairs[k][0], sub, nid.NIDCostParams(bins), max_fov=max_fov, cull=None, precision=precision)
+            sub.close()
+            build_s[0] += time.perf_counter() - t1
+            return c
+
     cal = calibration.VisualCameraCalibration(
-        [(p[0], None, None) for p in pairs], params, fused_nid_factory=fused_nid, fused_nearest_factory=fused_nearest, multi_factory=lambda init, costs: _Multi(init, costs))
+        [(p[0], None, None) for p in pairs], params, fused_nid_factory=fused_nid if selection is None else selected_nid,
+        fused_nearest_factory=fused_nearest if selection is None else selected_nearest, multi_factory=lambda init, costs: _Multi(init, costs))
     x = cal.calibrate(init_x)
     for c in clouds:
         c.close()
+    for m in masks:
+        if m is not None:
+            m.close()
     if stats is not None:
         stats.update(devices=min(ndev, len(pairs)), upload_s=upload_s, build_s=build_s[0], evaluations=int(sum(e.get("evaluations", 0) for e in cal.log)),
                      outer_iterations=len(cal.log))
@@ -125,6 +169,11 @@ def run(args, log=print):
         nelder_mead_convergence_criteria=args.nelder_mead_convergence_criteria)
     for b in bags:
         log(f"loaded {b.bag_name}: image {b.image.shape[1]}x{b.image.shape[0]}, {b.num_points} points")
+    sel = dataset.selection_options(args)
+    if sel is not None:
+        # (every mask is read and checked against its image here, on the host, before a cloud goes up)
+        sel["masks"] = [dataset.load_mask(args.data_path, b.bag_name, sel["mask"], b.image.shape, log=log) for b in bags]
+        log(f"selection: mask {sel['mask']}, margin {sel['margin']} px, range [{sel['min_range']}, {sel['max_range']}] m")
     if args.dry_run:
         return config, init_x, None
 
@@ -132,7 +181,10 @@ def run(args, log=print):
     t0 = time.time()
     # float32 bags go up as stored (nid.Cloud.from_float32): the CLI never widens a cloud on the host
     pairs = [(b.image, b.xyz_f32, b.intensities_f32) if b.xyz_f32 is not None else (b.image, b.points, b.intensities) for b in bags]
-    x, cal = calibrate_pairs(proj, pairs, init_x, params, precision=args.precision, stats=stats)
+    if sel is None:
+        x, cal = calibrate_pairs(proj, pairs, init_x, params, precision=args.precision, stats=stats)
+    else:
+        x, cal = calibrate_pairs(proj, pairs, init_x, params, precision=args.precision, stats=stats, selection=sel, log=log)
     elapsed = time.time() - t0
     ndev = stats["devices"]
     for entry in cal.log:

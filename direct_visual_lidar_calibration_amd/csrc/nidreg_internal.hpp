@@ -286,6 +286,7 @@ struct nidreg_cloud {
   int64_t n = 0;
   DeviceBuf d_pts;  // n x 4 doubles (x y z 1)
   DeviceBuf d_int;  // n doubles
+  int64_t sel_kept = -1, sel_masked = 0, sel_ranged = 0;  // a cloud made by nidreg_cloud_select: what the cull kept of its source, and what the mask / the range removed of that
 };
 
 // ---- everything below: declarations shared by the translation units of libnidreg.so's host side (nidreg_core / _plan / _multi / _rccl / _shard / _abi .hip)

@@ -620,6 +620,57 @@ def load_dataset(data_path, first_n_bags=None):
     return config, [VisualLiDARData(data_path, n) for n in names]
 
 
+def load_mask(data_path, bag_name, spec, image_shape, log=None):
+    """The image mask of one bag for ``--mask``: (H, W) uint8, non-zero = use, zero = ignore -- or ``None`` (the bag is used whole).
+    ``spec`` is ``None`` (no mask), a PNG path (one mask for every bag) or ``auto``: ``<data_path>/<bag>_mask.png`` if it exists,
+    else ``<data_path>/mask.png``, else none, which is logged.  Files are read with ``read_png_gray``.  A named file that does not
+    exist, and a mask whose size is not ``image_shape`` (H, W), are refused with a ValueError / FileNotFoundError that names the
+    file: host work only, before a device is touched."""
+    if spec is None:
+        return None
+    if spec == "auto":
+        candidates = [os.path.join(data_path, bag_name + "_mask.png"), os.path.join(data_path, "mask.png")]
+        path = next((p for p in candidates if os.path.exists(p)), None)
+        if path is None:
+            if log is not None:
+                log(f"{bag_name}: no {bag_name}_mask.png and no mask.png in {data_path}: the whole image is used")
+            return None
+    else:
+        path = str(spec)
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"error: failed to open mask {path}")
+    mask = read_png_gray(path)
+    if tuple(mask.shape) != (int(image_shape[0]), int(image_shape[1])):
+        raise ValueError(f"{path}: the mask is {mask.shape[1]}x{mask.shape[0]}, the image of {bag_name} {int(image_shape[1])}x{int(image_shape[0])}")
+    return mask
+
+
+def add_selection_options(parser):
+    """``--mask``, ``--mask_margin``, ``--min_range``, ``--max_range`` of ``calibrate`` and ``viewer`` (extensions; the reference has
+    no such options)."""
+    parser.add_argument("--mask", default=None, metavar="PATH|auto", help="8-bit PNG of the image's size, zero = ignore: one file for all bags, or 'auto' = <bag>_mask.png, else mask.png (extension)")
+    parser.add_argument("--mask_margin", type=int, default=None, help="pixels the ignored region is grown by, 0..64 (default 2: the reach of the B-spline) (extension)")
+    parser.add_argument("--min_range", type=float, default=None, help="ignore LiDAR points closer than this [m] (default 0) (extension)")
+    parser.add_argument("--max_range", type=float, default=None, help="ignore LiDAR points farther than this [m] (default inf) (extension)")
+
+
+def selection_options(args):
+    """``None`` when none of the four options is given (the caller's code path is then the one without them), else
+    ``{"mask": spec | None, "margin", "min_range", "max_range"}`` with the defaults filled in.  Refuses (SystemExit) a margin outside
+    [0, 64], a negative or NaN range and ``max_range < min_range``: host checks, before a device is touched."""
+    given = [getattr(args, k, None) for k in ("mask", "mask_margin", "min_range", "max_range")]
+    if all(v is None for v in given):
+        return None
+    margin = 2 if args.mask_margin is None else int(args.mask_margin)
+    lo = 0.0 if args.min_range is None else float(args.min_range)
+    hi = float("inf") if args.max_range is None else float(args.max_range)
+    if not 0 <= margin <= 64:
+        raise SystemExit("error: --mask_margin must lie in [0, 64]")
+    if not lo >= 0.0 or not hi >= lo:  # (a NaN fails both)
+        raise SystemExit("error: 0 <= --min_range <= --max_range expected")
+    return {"mask": args.mask, "margin": margin, "min_range": lo, "max_range": hi}
+
+
 def write_preprocessed(data_path, camera, bags, init_T_lidar_camera_tum=None, meta=None, lidar_images=None):
     """Write a directory in ``preprocess``'s output format (preprocess.cpp:150-232): ``calib.json``,
     ``<bag>.png``, ``<bag>.ply`` and, when given, ``<bag>_lidar_intensities.png`` /

@@ -3,7 +3,7 @@ intensity image and the matches between them, written to ``<bag>_matches.json`` 
 
     python -m direct_visual_lidar_calibration_amd.find_matches <data_path> [--max_keypoints 2048] [--nms_radius 4]
         [--fast_threshold T] [--max_distance D] [--ratio R] [--levels 8] [--rotate_camera 0] [--rotate_lidar 0] [--device 0]
-        [--picture | --picture_only]
+        [--picture | --picture_only] [--mask PATH|auto]
 
 This takes the place of the reference's ``scripts/find_matches_superglue.py`` and is NOT a port of it: SuperGlue needs pretrained
 weights under a non-commercial licence, and OpenCV.  What runs here is a classical stand-in (matching.py: FAST-9 over a 6/5 pyramid,
@@ -18,6 +18,9 @@ images side by side, every keypoint circled, every match a line coloured by its 
 script's: unrotated images, RGB colours, an integer resize).  ``--picture_only`` draws it from the ``<bag>_matches.json`` files already
 in the directory and runs no detection or matching; it draws a file the reference's SuperGlue script wrote just as well (float
 keypoints are truncated; a keypoint outside its image is refused).  ``--show_keypoints``, which opens a window, is not built.
+
+``--mask PATH|auto`` (extension; the files ``calibrate --mask`` reads, ``dataset.load_mask``) reports camera keypoints only on the
+mask's non-zero pixels: the mask is used as given, with no margin.
 """
 import argparse
 import json
@@ -42,6 +45,7 @@ def build_parser():
     p.add_argument("--rotate_camera", type=int, default=0, choices=(0, 90, 180, 270), help="rotate camera image before matching (CW)")
     p.add_argument("--rotate_lidar", type=int, default=0, choices=(0, 90, 180, 270), help="rotate LiDAR image before matching (CW)")
     p.add_argument("--device", type=int, default=0, help="GPU")
+    p.add_argument("--mask", default=None, metavar="PATH|auto", help="camera keypoints only where this 8-bit PNG is non-zero: one file for all bags, or 'auto' = <bag>_mask.png, else mask.png")
     g = p.add_mutually_exclusive_group()
     g.add_argument("--picture", action="store_true", help="also write <bag>_matches.png: both images, keypoints and matches")
     g.add_argument("--picture_only", action="store_true", help="draw <bag>_matches.png from the <bag>_matches.json already there; no detection or matching")
@@ -77,9 +81,14 @@ def run(args, log=print):
         indices = pose.read_index_image(os.path.join(args.data_path, bag_name + "_lidar_indices.png"))
         if indices.shape != lidar.shape:
             raise ValueError(f"{bag_name}: the LiDAR index image is {indices.shape[1]}x{indices.shape[0]}, the intensity image {lidar.shape[1]}x{lidar.shape[0]}")
+        extra = {}
+        if args.mask is not None:
+            cam_mask = dataset.load_mask(args.data_path, bag_name, args.mask, camera.shape, log=log)
+            if cam_mask is not None:
+                extra["camera_valid_mask"] = cam_mask
         result = matching.find_matches(np.ascontiguousarray(camera, dtype=np.uint8), np.ascontiguousarray(lidar, dtype=np.uint8), indices >= 0, max_keypoints=args.max_keypoints,
                                        nms_radius=args.nms_radius, fast_threshold=args.fast_threshold, max_distance=args.max_distance, ratio=args.ratio, levels=args.levels,
-                                       fill_passes=args.fill_passes, rotate_camera=args.rotate_camera, rotate_lidar=args.rotate_lidar, device=args.device)
+                                       fill_passes=args.fill_passes, rotate_camera=args.rotate_camera, rotate_lidar=args.rotate_lidar, device=args.device, **extra)
         path = os.path.join(args.data_path, bag_name + "_matches.json")
         with open(path, "w") as f:
             json.dump(result, f)

@@ -116,17 +116,27 @@ def unrotate_points(xy, angle, width, height):
 
 
 def find_matches(camera_u8, lidar_u8, lidar_valid_mask=None, max_keypoints=MAX_KEYPOINTS, nms_radius=NMS_RADIUS, fast_threshold=FAST_THRESHOLD, max_distance=MAX_DISTANCE, ratio=RATIO,
-                 levels=LEVELS, fill_passes=FILL_PASSES, rotate_camera=0, rotate_lidar=0, device=0, detect=None, match=None):
+                 levels=LEVELS, fill_passes=FILL_PASSES, rotate_camera=0, rotate_lidar=0, device=0, detect=None, match=None, camera_valid_mask=None):
     """Keypoints of both images and the accepted matches, as the dictionary ``<bag>_matches.json`` holds: ``kpts0`` / ``kpts1`` flat
     integer x, y lists (pixels of the UNROTATED images), ``matches`` one entry per camera keypoint (index into kpts1 or -1),
     ``confidence`` 1 - d / 256 for a matched row and 0 otherwise.  ``detect`` / ``match`` replace the device calls by functions of the same
-    signature without ``device`` (the checker runs the whole step on its numpy restatement)."""
+    signature without ``device`` (the checker runs the whole step on its numpy restatement).  ``camera_valid_mask`` (H, W; non-zero or
+    True = valid; the camera image's shape) keeps camera keypoints off its zero pixels: it is used as given, with no margin, turned
+    with ``rotate_camera``, and nothing is filled on the camera side (``fill_passes=0``: a masked region of a photograph holds pixels
+    that are unwanted, not missing)."""
     detect = detect or functools.partial(detect_features, device=device)
     match = match or functools.partial(match_features, device=device)
     cam = np.asarray(camera_u8)
     lid = np.asarray(lidar_u8)
     mask = None if lidar_valid_mask is None else np.asarray(lidar_valid_mask) != 0
-    k0, d0 = detect(rotate_cw(cam, rotate_camera), None, levels=levels, fast_threshold=fast_threshold, nms_radius=nms_radius, fill_passes=fill_passes, max_keypoints=max_keypoints)
+    if camera_valid_mask is None:
+        k0, d0 = detect(rotate_cw(cam, rotate_camera), None, levels=levels, fast_threshold=fast_threshold, nms_radius=nms_radius, fill_passes=fill_passes, max_keypoints=max_keypoints)
+    else:
+        cam_mask = np.asarray(camera_valid_mask) != 0
+        if cam_mask.shape != cam.shape:
+            raise ValueError("find_matches: camera_valid_mask must have the camera image's shape")
+        k0, d0 = detect(rotate_cw(cam, rotate_camera), rotate_cw(cam_mask, rotate_camera), levels=levels, fast_threshold=fast_threshold, nms_radius=nms_radius, fill_passes=0,
+                        max_keypoints=max_keypoints)
     k1, d1 = detect(rotate_cw(lid, rotate_lidar), None if mask is None else rotate_cw(mask, rotate_lidar), levels=levels, fast_threshold=fast_threshold, nms_radius=nms_radius,
                     fill_passes=fill_passes, max_keypoints=max_keypoints)
     num, den = ratio_fraction(ratio)

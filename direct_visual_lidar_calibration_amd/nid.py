@@ -15,6 +15,8 @@ here                                   reference
 ``CostCalculatorNID(proj, img8, ...)`` ``vlcal::CostCalculatorNID`` (cost_calculator_nid.cpp:13-17)
 ``CostCalculatorNID.calculate(T)``     ``CostCalculatorNID::calculate`` (:21-67)
 ``estimate_camera_fov(proj, size)``    ``vlcal::estimate_camera_fov`` (estimate_fov.cpp:36-51)
+``Mask(mask_u8, margin)``,             no counterpart (its users edit the PNG or the PLY by hand): image
+``Cloud.select(..., mask, ranges)``    regions and LiDAR ranges left out of the cost, selected on the GPU
 =====================================  ==========================================================
 
 All arithmetic of the cost functions runs in the HIP library behind ``include/nidreg.h``; this file
@@ -141,10 +143,89 @@ class Cloud:
         self.num_points = n
         return self
 
+    def select(self, proj, image_size, T, min_z, depth, mask=None, min_range=0.0, max_range=math.inf, return_indices=False):
+        """``nidreg_cloud_select``: the points that survive ``ViewCulling::cull`` at ``T`` (``T_camera_lidar`` 4x4; ``image_size`` =
+        (W, H), ``min_z`` and ``depth`` as in ``from_cloud``'s ``cull``), lie on a valid pixel of ``mask`` (a :class:`Mask`; ``None``:
+        every pixel) and whose LiDAR-frame range lies in [``min_range``, ``max_range``], as a new ``Cloud`` on the same device, in
+        input order -- compacted on the GPU, nothing but the count crosses to the host.  A handle built from it with ``cull=None``
+        is the one ``from_cloud(..., cull=(T, min_z, depth))`` builds from this cloud when nothing is masked or gated.
+        ``return_indices``: ``(cloud, indices int32 ascending)``."""
+        if proj is None:
+            raise ValueError("camera is None (create_camera failed)")
+        if mask is not None and not isinstance(mask, Mask):
+            raise TypeError("mask must be a nid.Mask (or None)")
+        T = np.ascontiguousarray(np.asarray(T, dtype=np.float64).reshape(4, 4))
+        idx = np.empty(max(self.num_points, 1), dtype=np.int32) if return_indices else None
+        out = ctypes.c_void_p()
+        count = ctypes.c_int64(0)
+        rc = self._lib.nidreg_cloud_select(self.c, proj.model_id, _dp(proj._intr5), _dp(proj._dist8), int(image_size[0]), int(image_size[1]), _dp(T), float(min_z), 1 if depth else 0,
+                                           None if mask is None else mask.m, float(min_range), float(max_range), ctypes.byref(out),
+                                           None if idx is None else idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(count))
+        _lib.check(rc, "nidreg_cloud_select")
+        sub = Cloud.__new__(Cloud)
+        sub._lib = self._lib
+        sub.c = out
+        sub.device = self.device
+        sub.num_points = int(count.value)
+        c3 = (ctypes.c_int64 * 3)()
+        _lib.check(self._lib.nidreg_cloud_select_counts(out, c3), "nidreg_cloud_select_counts")
+        sub.select_counts = {"culled_kept": int(c3[0]), "mask_removed": int(c3[1]), "range_removed": int(c3[2])}  # (of this cloud's points; for the log)
+        return (sub, idx[: sub.num_points].copy()) if return_indices else sub
+
+    def get(self):
+        """``nidreg_cloud_get``: ``(points (N, 4), intensities (N,))`` as the device holds them."""
+        n = ctypes.c_int64(0)
+        _lib.check(self._lib.nidreg_cloud_size(self.c, ctypes.byref(n)), "nidreg_cloud_size")
+        pts, inten = np.empty((n.value, 4)), np.empty(n.value)
+        _lib.check(self._lib.nidreg_cloud_get(self.c, _dp(pts), _dp(inten)), "nidreg_cloud_get")
+        return pts, inten
+
     def close(self):
         if getattr(self, "c", None):
             self._lib.nidreg_cloud_destroy(self.c)
             self.c = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Mask:
+    """An image mask resident on the GPU (``nidreg_mask_create``): ``mask_u8`` (H, W) uint8 or bool, non-zero = use, zero = ignore,
+    eroded by ``margin`` pixels (0..64) at creation -- a pixel stays valid iff no ignored pixel lies within ``margin`` of it; pixels
+    outside the image count as valid.  The default 2 is the reach of ``NIDCost``'s B-spline (columns x-1..x+2, rows y-1..y+2): no
+    ignored pixel is read at the pose a selection is made at.  ``Cloud.select(..., mask=...)`` consumes it."""
+
+    def __init__(self, mask_u8, margin=2, device=0):
+        lib = _lib.load()
+        self._lib = lib
+        m = np.asarray(mask_u8)
+        if m.dtype == np.bool_:
+            m = m.astype(np.uint8)
+        if m.ndim != 2 or m.dtype != np.uint8:
+            raise ValueError("mask must be a 2-D uint8 (or bool) array")
+        if m.size and (m.strides[1] != 1 or m.strides[0] < m.shape[1]):
+            m = np.ascontiguousarray(m)
+        h = ctypes.c_void_p()
+        rc = lib.nidreg_mask_create(int(device), m.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), m.shape[1], m.shape[0], m.strides[0] if m.size else m.shape[1], int(margin), ctypes.byref(h))
+        _lib.check(rc, "nidreg_mask_create")
+        self.m = h
+        self.device = int(device)
+        self.margin = int(margin)
+        self.shape = (m.shape[0], m.shape[1])
+
+    def eroded(self):
+        """``nidreg_mask_get``: the eroded mask, (H, W) uint8 (the minimum of the mask's bytes over the window; non-zero = valid)."""
+        out = np.empty(self.shape, dtype=np.uint8)
+        _lib.check(self._lib.nidreg_mask_get(self.m, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), out.strides[0]), "nidreg_mask_get")
+        return out
+
+    def close(self):
+        if getattr(self, "m", None):
+            self._lib.nidreg_mask_destroy(self.m)
+            self.m = None
 
     def __del__(self):
         try:

@@ -3,7 +3,7 @@
     python -m direct_visual_lidar_calibration_amd.viewer <data_path> [--dst_path <data_path>/viewer]
         [--transformation last|all|result|init_manual|init_auto] [--blend_weight 0.7] [--point_radius 1] [--alpha 178]
         [--orbit_deg -30,-15,15,30] [--view_size 1280x720] [--view_fov 60] [--first_n_bags N] [--disable_culling]
-        [--nid_bins 16] [--save_ply] [--device 0]
+        [--nid_bins 16] [--save_ply] [--device 0] [--mask PATH|auto] [--mask_margin 2] [--min_range 0] [--max_range inf]
 
 The reference's sixth executable (src/viewer.cpp, ``VisualLiDARVisualizer``, ``PointsColorUpdater``) shows the cloud coloured by the
 image under ``init_T_lidar_camera_auto``, ``init_T_lidar_camera`` or ``T_lidar_camera`` in a 3-D view the user turns: a wrong
@@ -17,6 +17,10 @@ selected transform:
 * ``<bag>_<label>_colored.ply``   (``--save_ply``) the cloud with those colours;
 * ``viewer.json``                 point counts, covered pixels and the NID (``CostCalculatorNID`` on the culled cloud) per label and
   bag, and the summed NID per label -- "is the result better than the guess" as a number next to the pictures.
+
+With ``--mask`` / ``--mask_margin`` / ``--min_range`` / ``--max_range`` (as in ``calibrate``) the overlay and the NID use the points
+``nid.Cloud.select`` keeps -- cull, eroded mask at the point's pixel, range gate --, and the overlay shows the ignored pixels of the
+eroded mask at half their grey value (``v >> 1``): what was left out is visible.  The orbit views keep the whole cloud.
 
 Colouring, culling, the cost and the renderer (``render.SplatRenderer``) all run on the GPU.  Deliberate differences from the
 reference: no window and no interaction; with no transform in ``calib.json`` the reference shows the identity under "NONE", this
@@ -62,6 +66,7 @@ def build_parser():
     p.add_argument("--nid_bins", type=int, default=16, help="Number of histogram bins for NID")
     p.add_argument("--save_ply", action="store_true", help="also write the coloured cloud")
     p.add_argument("--device", type=int, default=0, help="GPU to run on")
+    dataset.add_selection_options(p)
     return p
 
 
@@ -134,13 +139,29 @@ def overlay_and_nid(args, proj, bag, T_camera_lidar):
     """What one transform looks like on one bag's camera image, and its score: ``(overlay rgb (H, W, 3), its index image, the number
     of points the cost sees, NID)``.  The points are those ``ViewCulling`` keeps under the transform, drawn over the grey image through
     the camera's own model; the NID is ``CostCalculatorNID`` on the same points.  Reads ``args.disable_culling``, ``point_radius``,
-    ``alpha``, ``nid_bins`` and ``device``.  ``initial_guess_manual --candidates`` shows its 24 mountings with this too."""
+    ``alpha``, ``nid_bins`` and ``device``.  ``initial_guess_manual --candidates`` shows its 24 mountings with this too.
+    ``args.selection`` (``run`` sets it from the mask / range options; absent or ``None``: none given) narrows the points to
+    ``nid.Cloud.select``'s and halves the grey value of the eroded mask's ignored pixels in the overlay."""
     size = (bag.image.shape[1], bag.image.shape[0])
     points, intensities = bag.points, bag.intensities
-    culling = nid.ViewCulling(proj, size, nid.ViewCullingParams(not args.disable_culling), device=args.device)
-    keep = culling.cull(points, T_camera_lidar)
+    sel = getattr(args, "selection", None)
+    image = bag.image
+    if sel is None:
+        culling = nid.ViewCulling(proj, size, nid.ViewCullingParams(not args.disable_culling), device=args.device)
+        keep = culling.cull(points, T_camera_lidar)
+    else:
+        mask_u8 = sel["masks"].get(bag.bag_name)
+        mask = None if mask_u8 is None else nid.Mask(mask_u8, margin=sel["margin"], device=args.device)
+        cloud = nid.Cloud(points, intensities, device=args.device)
+        min_z = math.cos(nid.estimate_camera_fov(proj, size))  # view_culling.cpp:17, as nid.ViewCulling derives it
+        sub, keep = cloud.select(proj, size, T_camera_lidar, min_z, not args.disable_culling, mask=mask, min_range=sel["min_range"], max_range=sel["max_range"], return_indices=True)
+        sub.close()
+        cloud.close()
+        if mask is not None:
+            image = np.where(mask.eroded() == 0, bag.image >> 1, bag.image).astype(np.uint8)
+            mask.close()
     culled, culled_int = np.ascontiguousarray(points[keep]), np.ascontiguousarray(intensities[keep])
-    grey = np.ascontiguousarray(np.repeat(bag.image[:, :, None], 3, axis=2))
+    grey = np.ascontiguousarray(np.repeat(image[:, :, None], 3, axis=2))
     r = render.SplatRenderer(culled, device=args.device)
     r.set_colors(render.quantize_colors(render.colormap_turbo(culled_int)))
     overlay, index = r.draw(proj, size, T_camera_lidar, radius=args.point_radius, background=grey, alpha=args.alpha)
@@ -192,11 +213,15 @@ def run(args, log=print):
     if not 0 <= args.alpha <= 255 or not 0 <= args.point_radius <= 8:
         raise SystemExit("error: --alpha must lie in [0, 255] and --point_radius in [0, 8]")
 
+    sel = dataset.selection_options(args)
     config, bags = dataset.load_dataset(args.data_path, args.first_n_bags)
     model, intrinsics, distortion = dataset.camera_from_calib(config)
     proj = nid.create_camera(model, intrinsics, distortion)
     if proj is None:
         raise SystemExit(f"error: unknown camera model / wrong number of intrinsics: {model}")
+    if sel is not None:
+        sel["masks"] = {b.bag_name: dataset.load_mask(args.data_path, b.bag_name, sel["mask"], b.image.shape, log=log) for b in bags}
+    args.selection = sel
     dst = args.dst_path or os.path.join(args.data_path, "viewer")
     os.makedirs(dst, exist_ok=True)
 

@@ -33,6 +33,9 @@
  *                            vertex (src/vlcal/preprocess/preprocess.cpp:161-169); VisualLiDARData widens them to
  *                            doubles on the host after loading (src/vlcal/common/visual_lidar_data.cpp:19-26) --
  *                            here the floats are uploaded and widened on the GPU
+ *   nidreg_mask_*,           (no reference counterpart: its users edit the PNG or the PLY by hand) image regions and LiDAR
+ *   nidreg_cloud_select      ranges left out of the cost: the cull, an eroded 8-bit mask at the point's pixel and a range gate,
+ *                            compacted on the device into a new cloud
  *   nidreg_estimate_directions   vlcal::estimate_direction per keypoint (src/vlcal/common/estimate_fov.cpp:17-34; the loop of
  *                            src/vlcal/common/estimate_pose.cpp:46-51)
  *   nidreg_estimate_rotation_ransac  PoseEstimation::estimate_rotation_ransac, the hypothesis loop and the inlier flags
@@ -206,6 +209,49 @@ int nidreg_cloud_create_f32(int device_id, const float* points, int64_t point_st
                             nidreg_cloud** out);
 void nidreg_cloud_destroy(nidreg_cloud* cloud);
 int nidreg_create_from_cloud(const nidreg_desc* desc, const nidreg_cloud* cloud, const double* T_camera_lidar, double min_z, int enable_depth_buffer_culling, nidreg_handle** out);
+/* An EMPTY cloud (num_points = 0, or a selection that kept nothing) is a valid argument: the handle has no records, every
+ * evaluation runs on zero histograms, the NID is not finite and nidreg_eval returns NIDREG_FALSE like the functor's `return false`
+ * (nidreg_eval_iso hands the NaN back: CostCalculatorNID has no finite check). */
+int nidreg_cloud_size(const nidreg_cloud* cloud, int64_t* n);
+/* the cloud's points (n x 4 doubles: x y z 1) and intensities (n doubles) copied back to the host; either output may be NULL */
+int nidreg_cloud_get(const nidreg_cloud* cloud, double* points_out, double* intensities_out);
+
+/* Masks and range gates (no counterpart in the reference, whose users edit the PNG or the PLY by hand): leave image regions -- the
+ * vehicle's bonnet, a burnt-in timestamp, a strip of sky -- and LiDAR ranges -- returns too close to carry a usable intensity --
+ * out of the cost, on the device.
+ *
+ * nidreg_mask_create: mask = host, 8-bit, the camera image's size, row_stride bytes between rows; non-zero = use, zero = ignore
+ * (nidreg_features_detect's convention).  What is kept is its EROSION by margin pixels: eroded(x, y) = the minimum of the mask
+ * over [x - margin, x + margin] x [y - margin, y + margin] clipped to the image (pixels outside the image count as valid), so a
+ * pixel is valid iff no ignored pixel lies within margin of it.  The B-spline of NIDCost reads columns x-1..x+2 and rows y-1..y+2
+ * around a point's pixel: with margin >= 2 no ignored pixel is read at the pose the selection was made at.  nidreg_mask_get copies
+ * the eroded mask out (host, width x height bytes, row_stride between rows).
+ *
+ * nidreg_cloud_select: the points of `cloud` that
+ *   - survive ViewCulling::cull at T_camera_lidar (row-major 4x4), exactly as nidreg_view_culling / nidreg_create_from_cloud run it,
+ *   - lie on a valid pixel of the eroded mask (mask NULL: every pixel is valid) -- the pixel is the one the cull truncated the
+ *     projection to --, and
+ *   - satisfy min_range^2 <= (x x + y y) + z z <= max_range^2 in the cloud's own (LiDAR) frame, in double without contraction
+ *     (0 and +inf switch the gate off).  The gate runs AFTER the cull: a near point that is dropped still hides what is behind it.
+ * They become a new cloud *out (nidreg_cloud_destroy) in input order, points and intensities copied byte for byte; their ascending
+ * indices go to indices_out (nullable; capacity = the cloud's size) and their number to *count_out.  Zero selected points is not an
+ * error: *out is an empty cloud.  With mask = NULL and the default range the indices are nidreg_view_culling's, and a handle
+ * built from *out with T_camera_lidar = NULL has the records of the one nidreg_create_from_cloud builds from `cloud` with the cull
+ * (set desc.scale_points to the size of `cloud` for the same fixed-point unit beyond 2^22 points).  Deterministic: a flag pass, an
+ * exclusive scan of per-tile counts and a gather, NIDREG_SELECT_TILE points per workgroup, no atomics.
+ * NIDREG_ERR_INVALID before any device call: a NULL mask / out / count_out / cloud / parameter array, width or height outside
+ * [1, 16384], row_stride < width, margin outside [0, 64], a negative device_id, a mask whose size differs from width x height or
+ * that lives on another device than the cloud, min_range < 0, max_range < min_range, a NaN in either, an unknown model. */
+#define NIDREG_SELECT_TILE 1024
+typedef struct nidreg_mask nidreg_mask;
+int nidreg_mask_create(int device_id, const uint8_t* mask, int width, int height, int64_t row_stride, int margin, nidreg_mask** out);
+int nidreg_mask_get(const nidreg_mask* mask, uint8_t* eroded_out, int64_t row_stride);
+void nidreg_mask_destroy(nidreg_mask* mask);
+int nidreg_cloud_select(const nidreg_cloud* cloud, int model_id, const double* intrinsics, const double* distortion, int width, int height, const double* T_camera_lidar, double min_z,
+                        int enable_depth_buffer_culling, const nidreg_mask* mask, double min_range, double max_range, nidreg_cloud** out, int32_t* indices_out, int64_t* count_out);
+/* what became of the source's points, for a cloud nidreg_cloud_select made: counts3 = {kept by the cull, of those removed by the mask,
+ * of the rest removed by the range gate}; the cloud's size is [0] - [1] - [2].  NIDREG_ERR_INVALID for any other cloud. */
+int nidreg_cloud_select_counts(const nidreg_cloud* selected, int64_t* counts3);
 
 /* NIDCost::operator(): cost (+ gradient when grad7 != NULL) at se3 = [qx qy qz qw tx ty tz] */
 int nidreg_eval(nidreg_handle* h, const double* se3, double* cost, double* grad7);
