@@ -206,6 +206,8 @@ def load():
     lib.nidreg_cloud_size.argtypes = [ctypes.c_void_p, c_int64_p]
     lib.nidreg_cloud_get.argtypes = [ctypes.c_void_p, c_double_p, c_double_p]
     lib.nidreg_cloud_select_counts.argtypes = [ctypes.c_void_p, c_int64_p]
+    # test hook (csrc/nidreg_abi.hip, not declared in include/nidreg.h): a plain handle's records as the builder left them
+    lib.nidreg_debug_records.argtypes = [ctypes.c_void_p, c_int64_p, c_int64_p, ctypes.c_int64, c_double_p, c_int32_p, ctypes.c_int64]
     lib.nidreg_rccl_unique_id.argtypes = [ctypes.c_char_p]
     lib.nidreg_shard_comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]
     lib.nidreg_shard_attach_rccl.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
@@ -243,6 +245,24 @@ def stamp_or_refuse():
     if built != tree:
         raise SystemExit(f"refusing to stamp: libnidreg.so was built from kernel sources {built}, the tree holds {tree} (rebuild, then measure again)")
     return built
+
+
+def debug_records(handle):
+    """``nidreg_debug_records`` (a test hook): what the device record builder left in a plain handle, copied to the host --
+    ``dict(num_records, NG, GW, gcount int64[NG + 1], xyz float64 (n, 3), bin int32 (n,))``, records in stored order, float32
+    records widened (exact).  ``handle``: a ``nid`` cost object or a raw ``nidreg_handle``."""
+    import numpy as np
+
+    lib = load()
+    h = getattr(handle, "h", handle)
+    c3 = (ctypes.c_int64 * 3)()
+    check(lib.nidreg_debug_records(h, c3, None, 0, None, None, 0), "nidreg_debug_records")
+    n, NG, GW = int(c3[0]), int(c3[1]), int(c3[2])
+    gcount = np.zeros(NG + 1, dtype=np.int64)
+    xyz = np.zeros((n, 3), dtype=np.float64)
+    bins = np.zeros(n, dtype=np.int32)
+    check(lib.nidreg_debug_records(h, c3, gcount.ctypes.data_as(c_int64_p), NG + 1, xyz.ctypes.data_as(c_double_p), bins.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n), "nidreg_debug_records")
+    return dict(num_records=n, NG=NG, GW=GW, gcount=gcount, xyz=xyz, bin=bins)
 
 
 def last_error():

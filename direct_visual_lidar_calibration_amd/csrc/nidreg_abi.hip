@@ -715,6 +715,43 @@ int nidreg_debug_round_chunks(int per_cu, int num_cus, const int64_t* gcount, in
   return int(snap_to_groups(round_chunks(per_cu, num_cus, gcount[NG] - gcount[0]), gcount, NG, int64_t(per_cu) * num_cus));
 }
 
+/* test hook (tests/test_record_builder_gpu.py; not part of the drop-in surface): a read-only copy of what the record builder
+ * (nid_build.hip build_records_device) left in a plain handle.  counts3 = {records, NG, GW}; gcount_out (nullable, gcount_cap >=
+ * NG + 1 entries) = the record offsets of the column groups; xyz_out (3 doubles per record) / bin_out (nullable together, rec_cap
+ * >= records) = the records in stored order, Rec32 coordinates widened (exact), the bin as the kernels read it (the compact label
+ * when bins > 256).  A first call with null arrays gets the sizes.  Sharded handles (a master or a shard) are refused. */
+int nidreg_debug_records(nidreg_handle* h, int64_t* counts3, int64_t* gcount_out, int64_t gcount_cap, double* xyz_out, int32_t* bin_out, int64_t rec_cap) {
+  if (!h || !counts3) return fail(NIDREG_ERR_INVALID, "nidreg_debug_records: null argument");
+  if (h->set || h->is_shard) return fail(NIDREG_ERR_INVALID, "nidreg_debug_records: plain handles only (not a sharded master or a shard)");
+  if (h->NG < 1 || h->gcount.size() != size_t(h->NG) + 1) return fail(NIDREG_ERR_INVALID, "nidreg_debug_records: the handle has no group table");
+  const int64_t n = h->gcount[size_t(h->NG)];
+  if ((xyz_out == nullptr) != (bin_out == nullptr)) return fail(NIDREG_ERR_INVALID, "nidreg_debug_records: xyz_out and bin_out go together");
+  if (gcount_out && gcount_cap < int64_t(h->NG) + 1) return fail(NIDREG_ERR_INVALID, "nidreg_debug_records: gcount_cap below NG + 1");
+  if (xyz_out && rec_cap < n) return fail(NIDREG_ERR_INVALID, "nidreg_debug_records: rec_cap below the number of records");
+  counts3[0] = n, counts3[1] = h->NG, counts3[2] = h->GW;
+  if (gcount_out) std::copy(h->gcount.begin(), h->gcount.end(), gcount_out);
+  if (!xyz_out || n <= 0) return NIDREG_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  if (h->rec64) {
+    std::vector<Rec64> recs(static_cast<size_t>(n));
+    HIP_TRY(hipMemcpy(recs.data(), h->d_pts.as<void>(), size_t(n) * sizeof(Rec64), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; i++) {
+      const Rec64& r = recs[size_t(i)];
+      xyz_out[3 * i] = r.x, xyz_out[3 * i + 1] = r.y, xyz_out[3 * i + 2] = r.z;
+      bin_out[i] = int32_t(r.bin);
+    }
+  } else {
+    std::vector<Rec32> recs(static_cast<size_t>(n));
+    HIP_TRY(hipMemcpy(recs.data(), h->d_pts.as<void>(), size_t(n) * sizeof(Rec32), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; i++) {
+      const Rec32& r = recs[size_t(i)];
+      xyz_out[3 * i] = double(r.x), xyz_out[3 * i + 1] = double(r.y), xyz_out[3 * i + 2] = double(r.z);
+      bin_out[i] = int32_t(r.bin);
+    }
+  }
+  return NIDREG_OK;
+}
+
 void nidreg_trim(void) {
   const int ndev = nidreg_device_count();
   if (ndev <= 0) return;
