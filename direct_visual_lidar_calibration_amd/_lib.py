@@ -83,6 +83,7 @@ EXPORTS = [
     "nidreg_splat_create", "nidreg_splat_set_colors", "nidreg_splat_draw", "nidreg_splat_destroy",
     "nidreg_jpeg_info", "nidreg_jpeg_coefficients", "nidreg_jpeg_decode_gray", "nidreg_jpeg_get_timing",
     "nidreg_image_to_mono8", "nidreg_image_get_timing",
+    "nidreg_velodyne_decode", "nidreg_velodyne_get_timing",
     "nidreg_draw",
     "nidreg_mask_create", "nidreg_mask_get", "nidreg_mask_destroy", "nidreg_cloud_select", "nidreg_cloud_select_counts", "nidreg_cloud_size", "nidreg_cloud_get",
 ]
@@ -196,6 +197,10 @@ def load():
     # data as an address: the bytes may be a read-only view into a mapped bag file
     lib.nidreg_image_to_mono8.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_char_p, ctypes.c_int, c_uint8_p, ctypes.c_int64]
     lib.nidreg_image_get_timing.argtypes = [c_double_p]
+    # packets as an address: a read-only view into a mapped bag file, at any alignment
+    lib.nidreg_velodyne_decode.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                           c_float_p, c_int32_p]
+    lib.nidreg_velodyne_get_timing.argtypes = [c_double_p]
     lib.nidreg_draw.argtypes = [ctypes.c_int, c_uint8_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_uint8_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, c_int32_p, c_uint8_p]
     lib.nidreg_mask_create.argtypes = [ctypes.c_int, c_uint8_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
     lib.nidreg_mask_get.argtypes = [ctypes.c_void_p, c_uint8_p, ctypes.c_int64]

@@ -15,6 +15,10 @@ then the LiDAR's field of view from the first bag, both LiDAR images of every ba
 The bag reader is ``rosbag1`` (pure Python, no ROS); a frame's records are uploaded as they lie in the message and decoded on the
 GPU (``StaticPointCloudIntegrator.insert_cloud2``).  Differences from the reference:
 
+* a points topic of ``velodyne_msgs/VelodyneScan`` (the raw packets of a VLP-16 / HDL-32E, decoded on the GPU: ``--lidar_model``,
+  ``--velodyne_calibration``) or ``livox_ros_driver(2)/CustomMsg`` is read in a PointCloud2 topic's place (``lidar_messages``, unpinned
+  against the vendor drivers); with ``-a`` only in a bag that has no PointCloud2 topic.  The reference needs the driver's cloud;
+
 * ``-d / --dynamic_lidar_integration`` is refused here with status 1 and a message: the dynamic LiDAR integration (CT-GICP) is a
   command of its own, ``preprocess_dynamic``, which runs this module's ``run`` with ``odometry.DynamicPointCloudIntegrator``;
 * ROS2 bags (sqlite3 / mcap) are not read here: a file that does not start with ``#ROSBAG V2.0`` is not a bag (``valid_bag``).  They are
@@ -39,7 +43,7 @@ import sys
 
 import numpy as np
 
-from . import preprocess, rosbag1
+from . import lidar_messages, preprocess, rosbag1
 from .preprocess_map import _attach_values, parse_values
 
 VALID_CAMERA_MODELS = ("plumb_bob", "fisheye", "equidistant", "omnidir", "equirectangular")  # preprocess.cpp:362
@@ -62,7 +66,10 @@ def build_parser():
     p.add_argument("--camera_info_topic")
     p.add_argument("--image_topic", help="sensor_msgs/Image, or CompressedImage with a PNG or baseline JPEG payload; a JPEG is decoded as cv_bridge::toCvCopy(msg, mono8) decodes "
                                          "it (to BGR, then luma), which is not the Y plane cv::imread(path, 0) returns")
-    p.add_argument("--points_topic")
+    p.add_argument("--points_topic", help="sensor_msgs/PointCloud2, velodyne_msgs/VelodyneScan (the raw packets, decoded on the GPU) or livox_ros_driver(2)/CustomMsg")
+    p.add_argument("--lidar_model", default="auto", choices=("auto",) + lidar_messages.LIDAR_MODELS,
+                   help="packet layout and laser angles of a VelodyneScan topic: auto reads the product id of the first packet (extension)")
+    p.add_argument("--velodyne_calibration", help="the vendor driver's calibration YAML (16 or 32 lasers) in place of the built-in angles of a VelodyneScan topic (extension)")
     p.add_argument("--camera_model", default="auto", help="auto, atan, plumb_bob, fisheye(=equidistant), omnidir, or equirectangular")
     p.add_argument("--camera_intrinsics", help="camera intrinsic parameters [fx,fy,cx,cy(,xi)] (don't put spaces between values!!)")
     p.add_argument("--camera_distortion_coeffs", help="camera distortion parameters [k1,k2,p1,p2,k3] (don't put spaces between values!!)")
@@ -82,8 +89,9 @@ def find_bags(data_path, reader=rosbag1):
 
 def get_topics(args, bag, log=print, warn=_warn):
     """:266-317: ``(camera_info_topic, image_topic, points_topic)``; with ``-a`` by substring of the connection's type -- the LAST
-    match wins, with a warning --, then the named options for what is still empty"""
-    camera_info_topic = image_topic = points_topic = ""
+    match wins, with a warning --, then the named options for what is still empty.  A ``VelodyneScan`` or ``CustomMsg`` topic
+    (``lidar_messages``) is chosen only in a bag without any ``PointCloud2`` topic."""
+    camera_info_topic = image_topic = points_topic = packets_topic = ""
     if args.auto_topic:
         log(f"topics in {bag.path}:")
         for topic, type_ in bag.topics_and_types():
@@ -100,6 +108,11 @@ def get_topics(args, bag, log=print, warn=_warn):
                 if points_topic:
                     warn("warning: bag constains multiple points topics!!")
                 points_topic = topic
+            elif "VelodyneScan" in type_ or "CustomMsg" in type_:  # read in a PointCloud2 topic's place, never beside one
+                if packets_topic:
+                    warn("warning: bag constains multiple points topics!!")
+                packets_topic = topic
+    points_topic = points_topic or packets_topic
     camera_info_topic = camera_info_topic or args.camera_info_topic or ""
     image_topic = image_topic or args.image_topic or ""
     points_topic = points_topic or args.points_topic or ""
@@ -114,6 +127,14 @@ def _first(bag, topic, type_name, decode):
     return None if m is None else decode(m.data)
 
 
+def _first_points(bag, points_topic):
+    """The topic's first PointCloud2 message; without any, its first message of another kind ``lidar_messages`` reads"""
+    m = bag.first_message(points_topic, "PointCloud2")
+    if m is None:
+        m = next((m for m in bag.messages(points_topic) if lidar_messages.points_kind(m.type) is not None), None)
+    return m
+
+
 def get_intensity_channel(args, bag, points_topic, reader=rosbag1):
     """:319-347: the named channel, or with ``auto`` the field of the first cloud with the highest priority: ``reflectivity`` (2)
     beats ``intensity`` (1)"""
@@ -121,9 +142,10 @@ def get_intensity_channel(args, bag, points_topic, reader=rosbag1):
     if channel != "auto":
         return channel
     priorities = {"auto": -1, "intensity": 1, "reflectivity": 2}
-    cloud = _first(bag, points_topic, "PointCloud2", reader.decode_pointcloud2)
-    if cloud is None:
-        raise ValueError(f"error: no sensor_msgs/PointCloud2 message on points topic '{points_topic}' in {bag.path}")
+    m = _first_points(bag, points_topic)
+    if m is None:
+        raise ValueError(f"error: no sensor_msgs/PointCloud2, velodyne_msgs/VelodyneScan or livox_ros_driver(2)/CustomMsg message on points topic '{points_topic}' in {bag.path}")
+    cloud = reader.decode_points(m.type, m.data, header_only=True)  # (of a VelodyneScan only the fields: nothing is decoded for them)
     for f in cloud.fields:
         if f.name in priorities and priorities[channel] < priorities[f.name]:
             channel = f.name
@@ -195,8 +217,9 @@ def frame_times(cloud, where):
     return stamp, first, last, lambda: float(rosbag1.read_field_all(cloud, field).min()) / scale
 
 
-def integrate_bag(args, bag, points_topic, intensity_channel, integrator, warn=_warn, reader=rosbag1):
-    """:442-460: every PointCloud2 message of the topic, in the view's order, through the time keeper and into the integrator.
+def integrate_bag(args, bag, points_topic, intensity_channel, integrator, warn=_warn, reader=rosbag1, lidar=None):
+    """:442-460: every PointCloud2 message of the topic -- or the cloud ``reader.decode_points`` makes of a VelodyneScan or CustomMsg
+    message; ``lidar``: the run's ``lidar_messages.LidarOptions`` --, in the view's order, through the time keeper and into the integrator.
     Returns ``(frames inserted, frames skipped for a rewinding stamp, points skipped for a non-finite coordinate)``.  An integrator
     with ``insert_cloud2_timed`` (the dynamic one) also gets the frame's per-point times, as the time field and the affine map of
     ``TimeKeeper.process_times``."""
@@ -205,9 +228,9 @@ def integrate_bag(args, bag, points_topic, intensity_channel, integrator, warn=_
     inserted = rewound = nonfinite = 0
     for k, m in enumerate(bag.messages(points_topic)):
         where = f"(message {k} of points topic '{points_topic}' in {bag.path})"
-        if not (m.type.endswith("/PointCloud2") or m.type == "PointCloud2"):
+        if lidar_messages.points_kind(m.type) is None:
             break  # read_next returns nullptr at the first message that does not instantiate (src/preprocess_ros1.cpp:33-36)
-        cloud = reader.decode_pointcloud2(m.data)
+        cloud = reader.decode_points(m.type, m.data, lidar=lidar, device=getattr(args, "device", 0), where=where)
         names = [f.name for f in cloud.fields]
         if any(c not in names for c in ("x", "y", "z")):
             raise ValueError(f"error: missing point coordinate fields {where}: the cloud has {', '.join(names)}")
@@ -236,6 +259,17 @@ def integrate_bag(args, bag, points_topic, intensity_channel, integrator, warn=_
             raise ValueError(f"error: {e} {where}") from None
         inserted += 1
     return inserted, rewound, nonfinite
+
+
+def lidar_options(args, bag, points_topic, log=print):
+    """``--lidar_model`` and ``--velodyne_calibration`` as ``lidar_messages.LidarOptions`` when the points topic is a VelodyneScan one;
+    for any other topic they are ignored, with one logged line if either was given, and the result is ``None``"""
+    lidar_model, calibration = getattr(args, "lidar_model", "auto"), getattr(args, "velodyne_calibration", None)
+    if any(topic == points_topic and lidar_messages.points_kind(type_) == "VelodyneScan" for topic, type_ in bag.topics_and_types()):
+        return lidar_messages.LidarOptions(lidar_model, calibration)
+    if lidar_model != "auto" or calibration:
+        log(f"--lidar_model and --velodyne_calibration are ignored: points topic '{points_topic}' is not a velodyne_msgs/VelodyneScan topic")
+    return None
 
 
 def run(args, log=print, warn=_warn, integrator_factory=preprocess.StaticPointCloudIntegrator, reader=rosbag1):
@@ -268,6 +302,7 @@ def run(args, log=print, warn=_warn, integrator_factory=preprocess.StaticPointCl
     log(f"- camera_info: {camera_info_topic}")
     log(f"- image      : {image_topic}")
     log(f"- points     : {points_topic}")
+    lidar = lidar_options(args, first, points_topic, log=log)
     intensity_channel = get_intensity_channel(args, first, points_topic, reader=reader)
     log(f"intensity_channel: {intensity_channel}")
     camera_model, image_size, intrinsics, distortion = get_camera_params(args, first, camera_info_topic, image_topic, log=log, reader=reader)
@@ -283,7 +318,7 @@ def run(args, log=print, warn=_warn, integrator_factory=preprocess.StaticPointCl
         image = preprocess.equalize_hist(get_image(bag, image_topic, device=args.device, reader=reader))  # :414-419
         integ = integrator_factory(voxel_resolution=args.voxel_resolution, min_distance=args.min_distance, device=args.device)
         try:
-            inserted, rewound, nonfinite = integrate_bag(args, bag, points_topic, intensity_channel, integ, warn=warn, reader=reader)
+            inserted, rewound, nonfinite = integrate_bag(args, bag, points_topic, intensity_channel, integ, warn=warn, reader=reader, lidar=lidar)
             records = integ.get_records()
         finally:
             integ.close()

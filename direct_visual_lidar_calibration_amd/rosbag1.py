@@ -7,6 +7,7 @@ here                                            reference (through rosbag / cv_b
 ``topics_and_types(path)``                      ``rosbag::View::getConnections`` (:79-89)
 ``Bag(path).messages(topic)``                   ``rosbag::View(bag, rosbag::TopicQuery(topic))`` (:21-26, :54-63)
 ``decode_pointcloud2 / _image / _compressed_image / _camera_info``   ``m.instantiate<sensor_msgs::...>()``
+``decode_points`` (``lidar_messages``)          the vendor driver replayed between the bag and the points topic
 ``to_mono8`` / ``image_to_mono8`` / ``compressed_to_mono8``   ``cv_bridge::toCvCopy(msg, "mono8")`` (:126-135)
 ==============================================  =========================================================
 
@@ -242,6 +243,15 @@ def decode_pointcloud2(data):
     payload = np.frombuffer(r.take(r.u32()), dtype=np.uint8)
     is_dense = r.u8()
     return PointCloud2(stamp, frame_id, height, width, fields, is_bigendian, point_step, row_step, payload, is_dense)
+
+
+def decode_points(type_name, data, **kw):
+    """The message of a points topic by its connection type -- ``sensor_msgs/PointCloud2``, ``velodyne_msgs/VelodyneScan`` (decoded on
+    the GPU) or ``livox_ros_driver/CustomMsg`` (a view) -- as a ``PointCloud2`` tuple; ``None`` for any other type
+    (``lidar_messages.decode_points`` lists the keywords)"""
+    from . import lidar_messages
+
+    return lidar_messages.decode_points(type_name, data, cdr=False, **kw)
 
 
 def decode_image(data):

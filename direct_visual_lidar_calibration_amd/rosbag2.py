@@ -462,6 +462,14 @@ def decode_pointcloud2(data):
     return PointCloud2(stamp, frame_id, height, width, fields, is_bigendian, point_step, row_step, payload, is_dense)
 
 
+def decode_points(type_name, data, **kw):
+    """``rosbag1.decode_points`` for CDR blobs: ``sensor_msgs/msg/PointCloud2``, ``velodyne_msgs/msg/VelodyneScan`` (packets 1216 bytes
+    apart) or ``livox_ros_driver2/msg/CustomMsg`` (points 20 bytes apart) as a ``PointCloud2`` tuple; ``None`` for any other type"""
+    from . import lidar_messages
+
+    return lidar_messages.decode_points(type_name, data, cdr=True, **kw)
+
+
 def decode_image(data):
     """sensor_msgs/msg/Image; ``data`` is a zero-copy uint8 view"""
     r = _Cdr(data, "sensor_msgs/msg/Image")

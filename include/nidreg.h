@@ -673,6 +673,40 @@ int nidreg_image_to_mono8(int device_id, const uint8_t* data, int64_t size, int 
                           int64_t out_row_stride);
 int nidreg_image_get_timing(double* ms3);
 
+/* ---- Velodyne data packets to point records (csrc/nid_packet_kernels.hpp; Python: lidar_messages.py) ----------------------------
+ * What the vendor driver does between a bag of velodyne_msgs/VelodyneScan -- the raw UDP packets, 3 bytes a return -- and
+ * extract_raw_points (ros_cloud_converter.hpp): velodyne_pointcloud's RawData::unpack / unpack_vlp16, which turn packets into the
+ * x, y, z, intensity, time cloud the reference expects on its points topic.  Stateless (the device keeps only two 36000-entry
+ * cosine / sine tables, built once on the host with libm); all pointers are host memory; one workgroup per packet, no atomics: the
+ * same bytes on every run, restated byte for byte in tests/velodyne_oracle.py.  The rules restate the VLP-16 / HDL-32E manuals
+ * and velodyne_pointcloud's rawdata.cc from memory: the result is UNPINNED against velodyne_pointcloud and real recordings.
+ * SOURCE  packets: num_packets packets of 1206 data bytes, packet_stride bytes apart (1214 in a ROS1 message, 1216 in CDR), at any
+ * address; little-endian.  A packet is 12 blocks of 100 bytes -- uint16 flag (bytes FF EE), uint16 azimuth a[b] in 0.01 degree,
+ * 32 x (uint16 distance, uint8 reflectivity) --, the device's timestamp (4 bytes, unused), the return mode and the product id.
+ * OUTPUT  record (packet * 12 + block) * 32 + slot -- the byte order of the packet -- is 5 float32: x y z intensity time.
+ *   num_lasers 16 (two firings a block)  f = s / 16, l = s % 16, firing k = 2b + f; diff[b] = (a[b+1] - a[b] + 36000) % 36000 for
+ *                                        b < 11, diff[11] = diff[10], whatever the flags; % is the FLOORED modulo (Python's), so
+ *                                        diff and az lie in [0, 35999] for ANY uint16 azimuth fields, 36000..65535 included; az = (a[b] + (2 diff[b] (l + 24 f) + 48)
+ *                                        / 96) % 36000, floored: the driver's interpolation by (2.304 l + 55.296 f) / 110.592,
+ *                                        rounded half up
+ *   num_lasers 32 (one firing a block)   l = s, k = b, az = a[b] % 36000
+ *   time = float32(packet_times[p] + (k firing_period + l laser_period)), in double, in that order
+ *   a block whose flag is not 0xEEFF, or a raw distance of 0: x = y = z = quiet NaN (0x7FC00000), intensity 0, the time as above
+ *   else, in fp64 without contraction, with C, S = cos, sin of az * (pi / 18000) from the tables and the laser's row of `lasers`
+ *   (cos_vert, sin_vert, cos_rot_corr, sin_rot_corr, vert_offset, horiz_offset, dist_corr, 0):
+ *       d = raw distance_resolution + dist_corr;  cr = C cos_rc + S sin_rc;  sr = S cos_rc - C sin_rc;  xy = d cos_v - voff sin_v
+ *       xv = xy sr - hoff cr;  yv = xy cr + hoff sr;  zv = d sin_v + voff cos_v
+ *       x = float32(yv), y = float32(-xv), z = float32(zv) (the driver's turn into the ROS frame), intensity = float32(reflectivity)
+ *   returns_per_packet (nullable): per packet, the number of records that are not "no return".
+ * Refused with NIDREG_ERR_INVALID and a message, before the device is touched and with nothing written: num_lasers other than 16 or
+ * 32; packet_stride below 1206 or above 4096; num_packets outside [0, 65536]; a NULL packets, packet_times, lasers or records_out with
+ * num_packets > 0; a table entry, resolution or period that is not finite.  num_packets == 0 succeeds without a device.
+ *   nidreg_velodyne_get_timing  host wall-clock milliseconds of the calling thread's last nidreg_velodyne_decode: [0] allocation and
+ *                               upload, [1] the kernel (launch to idle), [2] copy back. */
+int nidreg_velodyne_decode(int device_id, const uint8_t* packets, int64_t num_packets, int64_t packet_stride, const double* packet_times, const double* lasers, int num_lasers,
+                           double distance_resolution, double firing_period, double laser_period, float* records_out, int32_t* returns_per_packet);
+int nidreg_velodyne_get_timing(double* ms3);
+
 /* ---- match pictures: a 2-D primitive rasteriser (csrc/nid_draw_kernels.hpp; Python: draw.py) ------------------------------------
  * What find_matches --picture and initial_guess_auto --picture draw with, in place of the reference script's OpenCV calls
  * (scripts/find_matches_superglue.py: both images side by side, keypoints circled, matches as lines).  Stateless; all pointers are
