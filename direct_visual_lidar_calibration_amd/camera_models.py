@@ -3,7 +3,7 @@
 Used for (a) synthetic-scene generation (``synth.py``: render an image / sample a cloud through a
 camera) and (b) as the camera half of the *second* oracle in ``tests/pyoracle.py`` (torch autograd
 supplies the Jacobian there).  It is NOT the product path: the product projects on the GPU in
-``csrc/nidreg_kernels.hip``; nothing here is called by ``NIDCost`` / ``CostCalculatorNID``.
+``csrc/nid_device.hpp`` (the projection models) from the kernels of ``csrc/nid_kernels.hpp``; nothing here is called by ``NIDCost`` / ``CostCalculatorNID``.
 
 Formulas follow the reference functors (include/camera/pinhole.hpp:11-52, fisheye.hpp:12-37,
 omnidir.hpp:12-42, equirectangular.hpp:12-29, atan.hpp:12-40, rational_polynomial.hpp:9-59) and

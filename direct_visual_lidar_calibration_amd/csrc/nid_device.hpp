@@ -913,21 +913,19 @@ struct Rec64 {  // 32 B: used only when the caller's doubles do not round-trip t
   uint64_t bin;
 };
 
-template <typename real>
-__device__ __forceinline__ void load_rec(const Rec32* p, real& x, real& y, real& z, uint32_t& bin) {
+__device__ __forceinline__ void load_rec(const Rec32* p, double& x, double& y, double& z, uint32_t& bin) {
   const float4 v = *reinterpret_cast<const float4*>(p);  // one 16 B/lane coalesced load
-  x = real(v.x);
-  y = real(v.y);
-  z = real(v.z);
+  x = v.x;
+  y = v.y;
+  z = v.z;
   bin = __float_as_uint(v.w);
 }
-template <typename real>
-__device__ __forceinline__ void load_rec(const Rec64* p, real& x, real& y, real& z, uint32_t& bin) {
+__device__ __forceinline__ void load_rec(const Rec64* p, double& x, double& y, double& z, uint32_t& bin) {
   const double2 a = reinterpret_cast<const double2*>(p)[0];
   const double2 b = reinterpret_cast<const double2*>(p)[1];
-  x = real(a.x);
-  y = real(a.y);
-  z = real(b.x);
+  x = a.x;
+  y = a.y;
+  z = b.x;
   bin = uint32_t(__double_as_longlong(b.y));
 }
 
@@ -939,9 +937,8 @@ template <int N>
 struct RawBatch<Rec32, N> {
   float4 v[N];
   __device__ __forceinline__ void load(const char* rec_base, uint32_t byte_off, int k) { v[k] = *reinterpret_cast<const float4*>(rec_base + size_t(byte_off)); }
-  template <typename real>
-  __device__ __forceinline__ void get(int k, real& x, real& y, real& z, uint32_t& bin) const {
-    x = real(v[k].x), y = real(v[k].y), z = real(v[k].z), bin = __float_as_uint(v[k].w);
+  __device__ __forceinline__ void get(int k, double& x, double& y, double& z, uint32_t& bin) const {
+    x = v[k].x, y = v[k].y, z = v[k].z, bin = __float_as_uint(v[k].w);
   }
   __device__ __forceinline__ void store(int k, Rec32* dst) const { *reinterpret_cast<float4*>(dst) = v[k]; }  // the raw record, as loaded (nid_fused.hpp: into LDS)
 };
@@ -952,9 +949,8 @@ struct RawBatch<Rec64, N> {
     a[k] = reinterpret_cast<const double2*>(rec_base + size_t(byte_off))[0];
     b[k] = reinterpret_cast<const double2*>(rec_base + size_t(byte_off))[1];
   }
-  template <typename real>
-  __device__ __forceinline__ void get(int k, real& x, real& y, real& z, uint32_t& bin) const {
-    x = real(a[k].x), y = real(a[k].y), z = real(b[k].x), bin = uint32_t(__double_as_longlong(b[k].y));
+  __device__ __forceinline__ void get(int k, double& x, double& y, double& z, uint32_t& bin) const {
+    x = a[k].x, y = a[k].y, z = b[k].x, bin = uint32_t(__double_as_longlong(b[k].y));
   }
   __device__ __forceinline__ void store(int k, Rec64* dst) const {
     reinterpret_cast<double2*>(dst)[0] = a[k];

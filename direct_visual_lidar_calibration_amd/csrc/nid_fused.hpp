@@ -98,7 +98,6 @@ __global__ __launch_bounds__(kThreads) void k_spline_fused(
   const Rec* __restrict__ pts, const Chunk* __restrict__ chunks, const uint8_t* __restrict__ img, int pitch, int W, int H, PoseParams<double> pose, CamParams<double> cam, int B, int GW,
   int cshift, double dn_scale, double inv_unit, u64* __restrict__ hist, GradTail gt, double* partials, double qx, double qy, double qz, double qw, double* out, double* out_host, double tag,
   unsigned int* counter, u64* barrier, u64 barrier_target, u64* barrier_flags, u64 barrier_epoch, unsigned long long timeout_ticks, int cap) {
-  typedef double real;
   constexpr int kT = kThreads;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const size_t region = grad_tile_region_bytes(B, GW, cshift);
@@ -123,7 +122,7 @@ __global__ __launch_bounds__(kThreads) void k_spline_fused(
   const int tile_w = tile_n << cshift;
   const uint32_t cmask = (1u << cshift) - 1u;
   const uint32_t lane_copy = uint32_t(tid) & cmask;
-  const real fW = real(W), fH = real(H);
+  const double fW = double(W), fH = double(H);
 
   // ------------------------------------------------------------------ phase A (spline_hist_body, generic tiling, one segment)
   stamp_stage(0);  // (-DNID_STAMP builds, tools/fused_stage_times.py: 0 entry, 1 points done, 2 flush issued, 3 barrier passed, 4 G tile built, 5 taps done, 6 ticket drawn, 7 results written)
@@ -135,12 +134,12 @@ __global__ __launch_bounds__(kThreads) void k_spline_fused(
     const char* rec_base = reinterpret_cast<const char*>(pts + ch.start);
     // the same instructions per point as k_spline_hist's `taps` (the bits a point contributes do not depend on the route);
     // additionally hands the 4 x 4 patch back for the stash
-    auto taps = [&](real uc, real vc, uint32_t bin, const BsplineScale& K, uint32_t* cols) {
+    auto taps = [&](double uc, double vc, uint32_t bin, const BsplineScale& K, uint32_t* cols) {
       const int kx = int(uc), ky = int(vc);
       double bxs[4];
-      real by[4];
-      bspline_scaled(double(m_abs(m_fract(uc))), K, bxs);
-      bspline6<real>(m_abs(m_fract(vc)), by);
+      double by[4];
+      bspline_scaled(m_abs(m_fract(uc)), K, bxs);
+      bspline6<double>(m_abs(m_fract(vc)), by);
       u64* col = tile + ((((bin - col0) * uint32_t(B)) << cshift) + lane_copy);
       load_patch(img, pitch, kx, ky, cols);
 #pragma unroll
@@ -148,42 +147,42 @@ __global__ __launch_bounds__(kThreads) void k_spline_fused(
 #pragma unroll
         for (int a = 0; a < 4; a++) {
           const uint32_t r = (cols[a] >> (8 * b)) & 0xffu;
-          atomicAdd(&col[r << cshift], to_fixed_dn(bxs[a], double(by[b])));
+          atomicAdd(&col[r << cshift], to_fixed_dn(bxs[a], by[b]));
         }
       }
     };
     RawBatch<Rec, kUnroll> rb;
     for (uint32_t base = 0; base < cnt; base += kT * kUnroll) {
-      real xs[kUnroll], ys[kUnroll], zs[kUnroll];
+      double xs[kUnroll], ys[kUnroll], zs[kUnroll];
       uint32_t bins_[kUnroll];
 #pragma unroll
       for (int k = 0; k < kUnroll; k++) rb.load(rec_base, min(base + uint32_t(k) * kT + tid, cnt - 1u) * uint32_t(sizeof(Rec)), k);
 #pragma unroll
-      for (int k = 0; k < kUnroll; k++) rb.template get<real>(k, xs[k], ys[k], zs[k], bins_[k]);
-      real us[kUnroll], vs[kUnroll];
+      for (int k = 0; k < kUnroll; k++) rb.get(k, xs[k], ys[k], zs[k], bins_[k]);
+      double us[kUnroll], vs[kUnroll];
       bool ins[kUnroll];
       bool all_in = true;
 #pragma unroll
       for (int k = 0; k < kUnroll; k++) {
         const uint32_t slot = base + uint32_t(k) * kT + tid;
         const bool valid = slot < cnt;
-        real cx, cy, cz;
-        transform_fma<real>(pose, xs[k], ys[k], zs[k], cx, cy, cz);
+        double cx, cy, cz;
+        transform_fma<double>(pose, xs[k], ys[k], zs[k], cx, cy, cz);
         if constexpr (FULL) {
-          ProjCtx<real> ctx;
-          project_fwd<MODEL, real>(cam, cx, cy, cz, us[k], vs[k], ctx);  // (u, v): the very call k_spline_grad makes -- and k_spline_hist's value
+          ProjCtx<double> ctx;
+          project_fwd<MODEL, double>(cam, cx, cy, cz, us[k], vs[k], ctx);  // (u, v): the very call k_spline_grad makes -- and k_spline_hist's value
           if (valid) {
 #pragma unroll
-            for (int j = 0; j < 6; j++) sd[size_t(2 + j) * cap + slot] = double(ctx.a[j]);
+            for (int j = 0; j < 6; j++) sd[size_t(2 + j) * cap + slot] = ctx.a[j];
             rb.store(k, &sr[slot]);  // (the raw record: x y z for M += gp p^T, the column)
           }
         } else {
-          project<MODEL, real, real, true>(cam, cx, cy, cz, us[k], vs[k]);
+          project<MODEL, double, double, true>(cam, cx, cy, cz, us[k], vs[k]);
         }
-        ins[k] = bool(int(valid) & int(us[k] >= real(0)) & int(us[k] < fW) & int(vs[k] >= real(0)) & int(vs[k] < fH));
+        ins[k] = bool(int(valid) & int(us[k] >= 0.0) & int(us[k] < fW) & int(vs[k] >= 0.0) & int(vs[k] < fH));
         if (valid) {
-          sd[size_t(0) * cap + slot] = ins[k] ? double(us[k]) : -1.0;  // an outlier fails phase B's range test by its stashed u
-          sd[size_t(1) * cap + slot] = double(vs[k]);
+          sd[size_t(0) * cap + slot] = ins[k] ? us[k] : -1.0;  // an outlier fails phase B's range test by its stashed u
+          sd[size_t(1) * cap + slot] = vs[k];
         }
         all_in = bool(int(all_in) & int(ins[k]));
       }
@@ -204,7 +203,7 @@ __global__ __launch_bounds__(kThreads) void k_spline_fused(
           KL.k05 = in ? KU.k05 : 0.0;
           KL.k1 = in ? KU.k1 : 0.0;
           uint32_t cols[4];
-          taps(in ? us[k] : real(0), in ? vs[k] : real(0), bins_[k], KL, cols);
+          taps(in ? us[k] : 0.0, in ? vs[k] : 0.0, bins_[k], KL, cols);
           if constexpr (FULL) {
             const uint32_t slot = base + uint32_t(k) * kT + tid;
             if (slot < cnt) sc[slot] = make_uint4(cols[0], cols[1], cols[2], cols[3]);
@@ -352,16 +351,16 @@ __global__ __launch_bounds__(kThreads) void k_spline_fused(
       for (int k = 0; k < kUnroll; k++) {
         const uint32_t slot = base + uint32_t(k) * kT + tid;
         if (slot >= cnt) break;
-        real x, y, z;
+        double x, y, z;
         uint32_t bin;
-        ProjCtx<real> ctx;
+        ProjCtx<double> ctx;
         uint32_t cols[4];
-        const real uu = sd[size_t(0) * cap + slot], vv = sd[size_t(1) * cap + slot];
-        const bool in = (uu >= real(0)) && (uu < fW) && (vv >= real(0)) && (vv < fH);
+        const double uu = sd[size_t(0) * cap + slot], vv = sd[size_t(1) * cap + slot];
+        const bool in = (uu >= 0.0) && (uu < fW) && (vv >= 0.0) && (vv < fH);
         if constexpr (FULL) {
-          load_rec<real>(&sr[slot], x, y, z, bin);
+          load_rec(&sr[slot], x, y, z, bin);
         } else {
-          rb.template get<real>(k, x, y, z, bin);
+          rb.get(k, x, y, z, bin);
         }
         if (in) {
           const int kx = int(uu), ky = int(vv);
@@ -371,34 +370,34 @@ __global__ __launch_bounds__(kThreads) void k_spline_fused(
             const uint4 c4 = sc[slot];
             cols[0] = c4.x, cols[1] = c4.y, cols[2] = c4.z, cols[3] = c4.w;
           } else {
-            real cx, cy, cz, u2, v2;
-            transform_fma<real>(pose, x, y, z, cx, cy, cz);
-            project_fwd<MODEL, real>(cam, cx, cy, cz, u2, v2, ctx);
+            double cx, cy, cz, u2, v2;
+            transform_fma<double>(pose, x, y, z, cx, cy, cz);
+            project_fwd<MODEL, double>(cam, cx, cy, cz, u2, v2, ctx);
             load_patch(img, pitch, kx, ky, cols);
           }
-          const real sx = m_abs(m_fract(uu)), sy = m_abs(m_fract(vv));
-          real bx[4], by[4], dbx[4], dby[4];
-          bspline6<real>(sx, bx);
-          bspline6<real>(sy, by);
-          bspline_deriv2<real>(sx, dbx);
-          bspline_deriv2<real>(sy, dby);
+          const double sx = m_abs(m_fract(uu)), sy = m_abs(m_fract(vv));
+          double bx[4], by[4], dbx[4], dby[4];
+          bspline6<double>(sx, bx);
+          bspline6<double>(sy, by);
+          bspline_deriv2<double>(sx, dbx);
+          bspline_deriv2<double>(sy, dby);
           const double* gcol = gtile + ((((bin - col0) * uint32_t(B)) << cshift) + lane_copy);
-          real gx = real(0), gy = real(0);
+          double gx = 0.0, gy = 0.0;
 #pragma unroll
           for (int b = 0; b < 4; b++) {
-            real sa = real(0), sb = real(0);
+            double sa = 0.0, sb = 0.0;
 #pragma unroll
             for (int a = 0; a < 4; a++) {
               const uint32_t r = (cols[a] >> (8 * b)) & 0xffu;
-              const real g = gcol[r << cshift];
+              const double g = gcol[r << cshift];
               sa = fma(g, dbx[a], sa);
               sb = fma(g, bx[a], sb);
             }
             gx = fma(sa, by[b], gx);
             gy = fma(sb, dby[b], gy);
           }
-          real gpr[3];
-          project_bwd<MODEL, real>(cam, ctx, gx, gy, gpr);
+          double gpr[3];
+          project_bwd<MODEL, double>(cam, ctx, gx, gy, gpr);
           const double gp0 = gpr[0], gp1 = gpr[1], gp2 = gpr[2];
           acc[0] = fma(gp0, x, acc[0]);
           acc[1] = fma(gp0, y, acc[1]);
@@ -418,7 +417,7 @@ __global__ __launch_bounds__(kThreads) void k_spline_fused(
   }
   // ------------------------------------------------------------------ end (k_spline_grad's epilogue)
   stamp_stage(5);
-  grad_reduce_store<kT>(acc, s_red, gtile, partials, blockIdx.x, gridDim.x);
+  grad_reduce_store<kT>(acc, gtile, partials, blockIdx.x, gridDim.x);
   // (the finalising workgroup reads the partials with agent-scope loads instead of an acquire fence + plain loads: no difference
   // measured -- 23.1 / 38.9 us either way at 100k / 1M points --, one L2 invalidation less)
   const bool last = last_workgroup_arrives<true, false>(counter, gridDim.x, s_flag);

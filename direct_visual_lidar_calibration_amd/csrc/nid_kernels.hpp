@@ -2,12 +2,12 @@
 //
 // One NIDCost evaluation (include/vlcal/costs/nid_cost.hpp:36-107 redesigned) -- the histogram buffer is zero on entry:
 // double-buffered, cleared by the previous evaluation's kernels; a caller-provided buffer is cleared with a memset:
-//   k_spline_hist   <model,rec,real,WIDE,MULTI,SEG>  stream the point records once; LDS-tiled fixed-point joint histogram
+//   k_spline_hist   <model,rec,WIDE,MULTI,SEG>       stream the point records once; LDS-tiled fixed-point joint histogram
 //   k_entropy       <MULTI>                          per block of 8 columns: sum p log(p + eps) (fixed point) and row sums, added
 //                                                    behind the histogram; cost-only evaluations: its last workgroup runs the
 //                                                    entropy tail (H_image, H_points, H_joint -> NID).  Not launched for
 //                                                    tables of <= 1024 cells in a cost+Jacobian evaluation (kSelfEntropyCells)
-//   k_spline_grad   <model,rec,real,GW1,MULTI,SEG>   prologue: the entropy tail on those sums (every workgroup, same integers),
+//   k_spline_grad   <model,rec,GW1,MULTI,SEG>        prologue: the entropy tail on those sums (every workgroup, same integers),
 //                                                    the G tile; stream the records again; contract dNID/dh with
 //                                                    d(weight)/d(p_cam), fold d(p_cam)/d(pose) into a 3x3 + 3 accumulator per
 //                                                    segment; last workgroup: reduce the partials, chain to
@@ -16,7 +16,10 @@
 // A pair spread over several GPUs by one process:  k_*_hist; k_entropy_repl (k_entropy + one exchange); k_spline_grad.
 // k_grad_final: stand-alone finalisation, launched only for an empty cloud (no gradient workgroup exists to do it).
 //
-// Point kernels: 256 threads (4 waves of 64; the WIDE histogram kernel 512); dynamic LDS only, base 16-B aligned.
+// Point kernels: 256 threads (4 waves of 64; the WIDE histogram kernel 512); dynamic LDS only, base 16-B aligned; one precision,
+// double (the scalar math library of nid_device.hpp stays generic).  Every #if in this file picks a numeric tunable, the NID_STAMP
+// instrumentation or which translation unit instantiates what -- none selects between two code paths (the A/B branches of
+// earlier rounds are gone: DESIGN.md section 3 names them and the commit that still has them).
 #pragma once
 #include "nid_device.hpp"
 #include "nid_multi.hpp"
@@ -25,12 +28,6 @@ namespace nidreg {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-#ifdef NID_EXP_HANDOFF
-// EXPERIMENT (VERDICT r4 #6 ii; profiles/r05_experiments.md): the histogram pass hands every record's projected (u, v) to the
-// gradient pass as an fp64 pair, 16 B / point, instead of the gradient pass recomputing the projection's value.  One buffer per
-// process (the experiment runs one handle), set by nidreg::set_handoff_buffer.
-static __device__ double2* g_uv_handoff;
-#endif
 #ifndef NID_UNROLL
 #define NID_UNROLL 4
 #endif
@@ -81,7 +78,6 @@ __device__ __forceinline__ void stamp_stage(int) {}
 // into rows 2 and 3) instead of __shfl_down's ds_bpermute pairs: 18 VALU instructions and two v_readlane per sum, no LDS
 // crossbar traffic -- the gradient kernel's epilogue runs twelve of these in every wave (144 ds_bpermute before, all of a
 // CU's workgroups at about the same time).  Fixed association: lane 63 ends up with ((rows 0 + 1) + (rows 2 + 3)).
-#ifndef NID_WAVE_SUM_SHFL
 template <int CTRL, int ROW_MASK, bool BOUND_ZERO>
 __device__ __forceinline__ double dpp_move(double v) {
   const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, BOUND_ZERO);
@@ -108,21 +104,8 @@ __device__ __forceinline__ unsigned int wave_sum(unsigned int v) {
   v += unsigned(__builtin_amdgcn_update_dpp(0, int(v), 0x143, 0xc, 0xf, false));
   return unsigned(__builtin_amdgcn_readlane(int(v), 63));
 }
-#else
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ unsigned int wave_sum(unsigned int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-#endif
 
 // the same for a 64-bit integer (fixed-point entropy partials, row sums): integer sums are order independent
-#ifndef NID_WAVE_SUM_SHFL
 template <int CTRL, int ROW_MASK, bool BOUND_ZERO>
 __device__ __forceinline__ long long dpp_move_i64(long long v) {
   const int lo = __builtin_amdgcn_update_dpp(0, int(uint32_t(u64(v))), CTRL, ROW_MASK, 0xf, BOUND_ZERO);
@@ -139,13 +122,6 @@ __device__ __forceinline__ long long wave_sum(long long v) {
   const int lo = __builtin_amdgcn_readlane(int(uint32_t(u64(v))), 63), hi = __builtin_amdgcn_readlane(int(uint32_t(u64(v) >> 32)), 63);
   return (long long)((u64(uint32_t(hi)) << 32) | u64(uint32_t(lo)));
 }
-#else
-__device__ __forceinline__ long long wave_sum(long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-#endif
 
 // Entropy terms t = p log(p + 1e-6) (|t| < 0.37; sum over a distribution <= log(bins^2) < 12) are accumulated as 64-bit
 // FIXED POINT with 50 fractional bits: t + 6 lies in [4, 8), where a double's ulp is 2^-50, so bits(t + 6) - bits(6) is
@@ -272,19 +248,17 @@ __device__ __forceinline__ void grad_final_body(const double* partials, int nblo
 // 84.0 -> 78.6 us; the thresholds hardly matter (quarters, 1/2-3/4-7/8, per point instead of per batch: all within 1 us); a
 // purely phase-based toggle (either direction) or a rotating priority gain half as much -- what helps is that co-resident
 // waves stop being served strictly by age.
-// `done` / `total` are uniform: scalar compares only.  -DNID_NO_PRIO builds the kernels without it (A/B runs).
+// `done` / `total` are uniform: scalar compares only.
 // `on` (uniform, a kernel argument): the host sets it when the evaluation is the only one in flight on its device -- with
 // several callers' kernels sharing the GPU (the reference's OpenMP loop over pairs, visual_camera_calibration.cpp:161) the
 // rule made the last kernels 5-16 % slower (profiles/archive/r02h_multi_pair_threads.txt), so they run without it.
 __device__ __forceinline__ void set_progress_priority(bool on, uint32_t done, uint32_t total) {
-#ifndef NID_NO_PRIO
   if (!on) return;
   const uint32_t quarter = total >> 2;
   if (done < quarter) __builtin_amdgcn_s_setprio(3);
   else if (done < 2u * quarter) __builtin_amdgcn_s_setprio(2);
   else if (done < 3u * quarter) __builtin_amdgcn_s_setprio(1);
   else __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 // ---- one pair spread over several GPUs (protocol: see the k_entropy_repl section below)
@@ -391,10 +365,10 @@ struct Segments {
 __device__ __forceinline__ void drain_vmem() { __builtin_amdgcn_s_waitcnt(0x0F70); }  // vmcnt(0), expcnt / lgkmcnt untouched
 
 // The pass as a device function.  `smem` = the workgroup's dynamic LDS (tile at its start); kT = threads per workgroup.
-template <int MODEL, typename Rec, typename real, bool WIDE, bool SEG, int kT>
+template <int MODEL, typename Rec, bool WIDE, bool SEG, int kT>
 __device__ __forceinline__ void spline_hist_body(
-  const Rec* __restrict__ pts, const Chunk ch, const uint32_t* __restrict__ gend, const uint8_t* __restrict__ img, int pitch, int W, int H, const PoseParams<real>& pose,
-  const CamParams<real>& cam, int B, int GW, int cshift, double dn_scale, u64* __restrict__ hist, unsigned char* smem, bool prio) {
+  const Rec* __restrict__ pts, const Chunk ch, const uint32_t* __restrict__ gend, const uint8_t* __restrict__ img, int pitch, int W, int H, const PoseParams<double>& pose,
+  const CamParams<double>& cam, int B, int GW, int cshift, double dn_scale, u64* __restrict__ hist, unsigned char* smem, bool prio) {
   u64* tile = reinterpret_cast<u64*>(smem);
   if (WIDE) {  // the specialisation's tiling is fixed: compile-time constants instead of three SGPRs
     B = 256;
@@ -416,7 +390,7 @@ __device__ __forceinline__ void spline_hist_body(
   stamp_stage(0);
   if (tid == 0) *s_inl = 0;
 
-  const real fW = real(W), fH = real(H);
+  const double fW = double(W), fH = double(H);
   const uint32_t lane_copy = uint32_t(tid) & cmask;
   unsigned int inl = 0;
   const BsplineScale KU = bspline_scale(dn_scale);  // uniform: the x-weight polynomial's constants in fixed-point units
@@ -444,14 +418,14 @@ __device__ __forceinline__ void spline_hist_body(
     // K is the uniform constant set when every lane of the wave holds an inlier (the common case after view
     // culling), a per-lane set zeroed for outliers / padding slots otherwise: the same arithmetic either way, so
     // the bits a point contributes do not depend on its wave neighbours (tiling independence).
-    auto taps = [&](real uc, real vc, uint32_t bin, const BsplineScale& K) {
+    auto taps = [&](double uc, double vc, uint32_t bin, const BsplineScale& K) {
       const int kx = int(uc), ky = int(vc);  // uc, vc >= 0: truncation is the floor knot (nid_cost.hpp:52)
       double bxs[4];
-      real by[4];
+      double by[4];
       // |.|: a projected coordinate of exactly -0.0 passes `>= 0`, and a -0.0 fraction would put a sign bit into a
       // weight (to_fixed_dn reads bit patterns); the modifier folds into the consuming instructions
-      bspline_scaled(double(m_abs(m_fract(uc))), K, bxs);
-      bspline6<real>(m_abs(m_fract(vc)), by);
+      bspline_scaled(m_abs(m_fract(uc)), K, bxs);
+      bspline6<double>(m_abs(m_fract(vc)), by);
       u64* col = tile + ((((bin - col0) * uint32_t(B)) << cshift) + lane_copy);
       // padded bin image: tap (a,b) of knot (kx,ky) is padded pixel (kx + a, ky + b) (edge-replicated,
       // which is the reference's clamp of knots_x / knots_y, nid_cost.hpp:70-73)
@@ -464,10 +438,10 @@ __device__ __forceinline__ void spline_hist_body(
           if (WIDE) {
             typedef __attribute__((address_space(3))) u64 lds_u64_t;
             const uint32_t addr = __builtin_amdgcn_perm(cols[a], lane_copy << 3, 0x0c0c0000u | (uint32_t(4 + b) << 8));  // [0, 0, byte b of cols[a], copy * 8]
-            __hip_atomic_fetch_add((lds_u64_t*)(uintptr_t)addr, to_fixed_dn(bxs[a], double(by[b])), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add((lds_u64_t*)(uintptr_t)addr, to_fixed_dn(bxs[a], by[b]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           } else {
             const uint32_t r = (cols[a] >> (8 * b)) & 0xffu;
-            atomicAdd(&col[r << cshift], to_fixed_dn(bxs[a], double(by[b])));  // v_mul_f64 + ds_add_u64
+            atomicAdd(&col[r << cshift], to_fixed_dn(bxs[a], by[b]));  // v_mul_f64 + ds_add_u64
           }
         }
       }
@@ -480,13 +454,13 @@ __device__ __forceinline__ void spline_hist_body(
     auto batch = [&](uint32_t base, auto guarded) {
       constexpr bool GUARDED = decltype(guarded)::value;
       set_progress_priority(prio, seg.pos - ch.start + base, ch.count);
-      real xs[kUnroll], ys[kUnroll], zs[kUnroll];
+      double xs[kUnroll], ys[kUnroll], zs[kUnroll];
       uint32_t bins_[kUnroll];
 #pragma unroll
       for (int k = 0; k < kUnroll; k++) rb.load(rec_base, (GUARDED ? min(base + uint32_t(k) * kT + tid, cnt - 1u) : base + uint32_t(k) * kT + tid) * uint32_t(sizeof(Rec)), k);
 #pragma unroll
-      for (int k = 0; k < kUnroll; k++) rb.template get<real>(k, xs[k], ys[k], zs[k], bins_[k]);
-      real us[kUnroll], vs[kUnroll];
+      for (int k = 0; k < kUnroll; k++) rb.get(k, xs[k], ys[k], zs[k], bins_[k]);
+      double us[kUnroll], vs[kUnroll];
       bool ins[kUnroll];
       bool all_in = true;
       // Round 6: a slot of the batch that lies past the end of the segment for EVERY lane of this wave is skipped (a scalar compare on
@@ -500,21 +474,18 @@ __device__ __forceinline__ void spline_hist_body(
 #pragma unroll
       for (int k = 0; k < kUnroll; k++) {
         if (!live[k]) {
-          us[k] = vs[k] = real(0);
+          us[k] = vs[k] = 0.0;
           ins[k] = false;
           all_in = false;  // (the batch takes the per-lane-constant tap path below, which skips this slot)
           continue;
         }
         const bool valid = !GUARDED || base + uint32_t(k) * kT + tid < cnt;
-        real cx, cy, cz;
-        transform_fma<real>(pose, xs[k], ys[k], zs[k], cx, cy, cz);
-        project<MODEL, real, real, true>(cam, cx, cy, cz, us[k], vs[k]);
+        double cx, cy, cz;
+        transform_fma<double>(pose, xs[k], ys[k], zs[k], cx, cy, cz);
+        project<MODEL, double, double, true>(cam, cx, cy, cz, us[k], vs[k]);
         // floor(u) in [0,W) and floor(v) in [0,H); NaN / inf / overflow compare false -> outlier
         // (the reference's int conversion sends those to INT_MIN, nid_cost.hpp:52-58)
-        ins[k] = bool(int(valid) & int(us[k] >= real(0)) & int(us[k] < fW) & int(vs[k] >= real(0)) & int(vs[k] < fH));  // no short circuit: branch-free
-#ifdef NID_EXP_HANDOFF
-        if (valid) g_uv_handoff[seg.pos + base + uint32_t(k) * kT + tid] = make_double2(double(us[k]), double(vs[k]));
-#endif
+        ins[k] = bool(int(valid) & int(us[k] >= 0.0) & int(us[k] < fW) & int(vs[k] >= 0.0) & int(vs[k] < fH));  // no short circuit: branch-free
         inl += ins[k] ? 1u : 0u;
         all_in = bool(int(all_in) & int(ins[k]));
       }
@@ -533,7 +504,7 @@ __device__ __forceinline__ void spline_hist_body(
           KL.k46 = in ? KU.k46 : 0.0;
           KL.k05 = in ? KU.k05 : 0.0;
           KL.k1 = in ? KU.k1 : 0.0;
-          taps(in ? us[k] : real(0), in ? vs[k] : real(0), bins_[k], KL);
+          taps(in ? us[k] : 0.0, in ? vs[k] : 0.0, bins_[k], KL);
         }
       }
     };
@@ -580,9 +551,9 @@ __host__ __device__ __forceinline__ size_t spline_hist_lds_bytes(int B, int GW, 
 // waves per SIMD the WIDE kernel is compiled for: two 8-wave workgroups per CU need <= 128 VGPRs; both the straight-line and
 // the looped kernels land there by themselves (the `atan` model's Dual3 forward mode holds ~164 either way), so no bound is
 // imposed (a forced bound made the compiler give up the four-deep record prefetch: +20-30 % on the looped kernel).
-template <int MODEL, typename Rec, typename real, bool WIDE, bool MULTI, bool SEG>
+template <int MODEL, typename Rec, bool WIDE, bool MULTI, bool SEG>
 __global__ __launch_bounds__(WIDE ? kWideThreads : kThreads) void k_spline_hist(
-  const Rec* __restrict__ pts, const Chunk* __restrict__ chunks, const uint32_t* __restrict__ gend, const uint8_t* __restrict__ img, int pitch, int W, int H, PoseParams<real> pose, CamParams<real> cam, int B,
+  const Rec* __restrict__ pts, const Chunk* __restrict__ chunks, const uint32_t* __restrict__ gend, const uint8_t* __restrict__ img, int pitch, int W, int H, PoseParams<double> pose, CamParams<double> cam, int B,
   int GW, int cshift, double dn_scale, u64* __restrict__ hist, int prio,
   const MultiEntry* __restrict__ multi, typename multi_dyn_of<MULTI>::type dyn) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -597,7 +568,7 @@ __global__ __launch_bounds__(WIDE ? kWideThreads : kThreads) void k_spline_hist(
     hist = as_global(e.hist_buf[dyn.cur[pair]]);
     dn_scale = e.k16;
   }
-  spline_hist_body<MODEL, Rec, real, WIDE, SEG, kT>(pts, ch, gend, img, pitch, W, H, pose, cam, B, GW, cshift, dn_scale, hist, smem, prio != 0);
+  spline_hist_body<MODEL, Rec, WIDE, SEG, kT>(pts, ch, gend, img, pitch, W, H, pose, cam, B, GW, cshift, dn_scale, hist, smem, prio != 0);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -613,7 +584,7 @@ __global__ __launch_bounds__(WIDE ? kWideThreads : kThreads) void k_spline_hist(
 // repeat the point in the reference's exact expression order.  The integer histogram stays bit-exact against the CPU
 // (tests: every model and bin count, 10M points, and points placed 1e-13 ... 1e-9 around every kind of decision boundary).
 //
-// The bound.  Both tiers evaluate the same real-valued functions of the same inputs; with eps = 2^-52:
+// The bound.  Both tiers evaluate the same functions (in exact arithmetic) of the same inputs; with eps = 2^-52:
 //   c = M p + t:   |c_fast - c_exact| <= e1 = 8 eps (rmax (|x| + |y| + |z|) + tmax)   per component (three products, three
 //                  sums, either association; rmax / tmax = largest |entry| of the rotation block / the translation);
 //   zn = cz / |c|: |d zn| <= sqrt(3) e1 / |c| + 16 eps                                 -> band bz = 8 e1 / |c| + 4e-14
@@ -675,13 +646,13 @@ __host__ __device__ __forceinline__ size_t nearest_hist_lds_bytes(int B, int GW,
 #ifndef NID_NEAREST_EQUIRECT_WAVES
 #define NID_NEAREST_EQUIRECT_WAVES 4
 #endif
-constexpr int nearest_min_waves(int model, bool is_double, bool rec32, bool seg) {
-  return (is_double && rec32 && !seg) ? (model == MODEL_PLUMB_BOB ? 5 : (model == MODEL_FISHEYE ? 4 : (model == MODEL_EQUIRECT ? NID_NEAREST_EQUIRECT_WAVES : 1))) : 1;
+constexpr int nearest_min_waves(int model, bool rec32, bool seg) {
+  return (rec32 && !seg) ? (model == MODEL_PLUMB_BOB ? 5 : (model == MODEL_FISHEYE ? 4 : (model == MODEL_EQUIRECT ? NID_NEAREST_EQUIRECT_WAVES : 1))) : 1;
 }
-template <int MODEL, typename Rec, typename real, bool MULTI, bool SEG>
-__global__ __launch_bounds__(kThreads, nearest_min_waves(MODEL, std::is_same<real, double>::value, sizeof(Rec) == sizeof(Rec32), SEG)) void k_nearest_hist(
-  const Rec* __restrict__ pts, const Chunk* __restrict__ chunks, const uint32_t* __restrict__ gend, const uint8_t* __restrict__ img, int pitch, int W, int H, IsoParams<real> iso,
-  CamParams<real> cam, int B, int GW, int cshift, real cos_fov, NearestFast fast, u64* __restrict__ hist,
+template <int MODEL, typename Rec, bool MULTI, bool SEG>
+__global__ __launch_bounds__(kThreads, nearest_min_waves(MODEL, sizeof(Rec) == sizeof(Rec32), SEG)) void k_nearest_hist(
+  const Rec* __restrict__ pts, const Chunk* __restrict__ chunks, const uint32_t* __restrict__ gend, const uint8_t* __restrict__ img, int pitch, int W, int H, IsoParams<double> iso,
+  CamParams<double> cam, int B, int GW, int cshift, double cos_fov, NearestFast fast, u64* __restrict__ hist,
   const MultiEntry* __restrict__ multi, typename multi_dyn_of<MULTI>::type dyn) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint32_t* tile = reinterpret_cast<uint32_t*>(smem);
@@ -703,23 +674,23 @@ __global__ __launch_bounds__(kThreads, nearest_min_waves(MODEL, std::is_same<rea
   }
   if (tid == 0) *s_inl = 0;
 
-  const real fW = real(W), fH = real(H);
+  const double fW = double(W), fH = double(H);
   unsigned int inl = 0;
-  constexpr bool kFastTier = (MODEL == MODEL_PLUMB_BOB || MODEL == MODEL_FISHEYE || MODEL == MODEL_OMNIDIR || MODEL == MODEL_EQUIRECT) && std::is_same<real, double>::value;
+  constexpr bool kFastTier = MODEL == MODEL_PLUMB_BOB || MODEL == MODEL_FISHEYE || MODEL == MODEL_OMNIDIR || MODEL == MODEL_EQUIRECT;
 
   // the reference's expression order (cost_calculator_nid.cpp:30-47): +, -, *, /, sqrt bit-identical to the CPU's
-  auto exact = [&](real x, real y, real z, bool& in, int& px, int& py) {
+  auto exact = [&](double x, double y, double z, bool& in, int& px, int& py) {
     // Eigen 4x4 * (x y z 1): ((m0 x + m1 y) + m2 z) + m3 * 1
-    const real cx = ((iso.m[0] * x + iso.m[1] * y) + iso.m[2] * z) + iso.m[3];
-    const real cy = ((iso.m[4] * x + iso.m[5] * y) + iso.m[6] * z) + iso.m[7];
-    const real cz = ((iso.m[8] * x + iso.m[9] * y) + iso.m[10] * z) + iso.m[11];
-    const real n2 = (cx * cx + cy * cy) + cz * cz;
-    const real zn = n2 > real(0) ? cz / m_sqrt(n2) : cz;
+    const double cx = ((iso.m[0] * x + iso.m[1] * y) + iso.m[2] * z) + iso.m[3];
+    const double cy = ((iso.m[4] * x + iso.m[5] * y) + iso.m[6] * z) + iso.m[7];
+    const double cz = ((iso.m[8] * x + iso.m[9] * y) + iso.m[10] * z) + iso.m[11];
+    const double n2 = (cx * cx + cy * cy) + cz * cz;
+    const double zn = n2 > 0.0 ? cz / m_sqrt(n2) : cz;
     const bool in_fov = !(zn < cos_fov);  // out of FoV otherwise (cost_calculator_nid.cpp:32)
-    real u, v;
-    project<MODEL, real, real>(cam, cx, cy, cz, u, v);
+    double u, v;
+    project<MODEL, double, double>(cam, cx, cy, cz, u, v);
     // trunc(u) in [0,W)  <=>  -1 < u < W ; NaN false (cost_calculator_nid.cpp:37-41)
-    in = in_fov && (u > real(-1)) && (u < fW) && (v > real(-1)) && (v < fH);
+    in = in_fov && (u > -1.0) && (u < fW) && (v > -1.0) && (v < fH);
     px = in ? int(u) : 0;  // truncation toward zero
     py = in ? int(v) : 0;
   };
@@ -741,12 +712,12 @@ __global__ __launch_bounds__(kThreads, nearest_min_waves(MODEL, std::is_same<rea
     // the body under this kernel's register bounds spill: plumb_bob 60 -> 98 us per evaluation, fisheye 53 -> 57, omnidir 66 -> 72,
     // equirectangular 87 -> 85; profiles/r06_experiments.md.  One guarded loop.)
     for (uint32_t base = 0; base < cnt; base += kThreads * kUnroll) {
-      real xs[kUnroll], ys[kUnroll], zs[kUnroll];
+      double xs[kUnroll], ys[kUnroll], zs[kUnroll];
       uint32_t bins_[kUnroll];
 #pragma unroll
       for (int k = 0; k < kUnroll; k++) {
         const uint32_t ii = min(base + uint32_t(k) * kThreads + tid, cnt - 1u);
-        load_rec<real>(recs + ii, xs[k], ys[k], zs[k], bins_[k]);
+        load_rec(recs + ii, xs[k], ys[k], zs[k], bins_[k]);
       }
       bool ins[kUnroll], need[kUnroll];
       int pxs[kUnroll], pys[kUnroll];
@@ -764,9 +735,9 @@ __global__ __launch_bounds__(kThreads, nearest_min_waves(MODEL, std::is_same<rea
         for (int k = 0; k < kUnroll; k++) {  // branch-free: the four points interleave
           const bool valid = need[k];
           const double x = xs[k], y = ys[k], z = zs[k];
-          const double cx = fma(double(iso.m[2]), z, fma(double(iso.m[1]), y, fma(double(iso.m[0]), x, double(iso.m[3]))));
-          const double cy = fma(double(iso.m[6]), z, fma(double(iso.m[5]), y, fma(double(iso.m[4]), x, double(iso.m[7]))));
-          const double cz = fma(double(iso.m[10]), z, fma(double(iso.m[9]), y, fma(double(iso.m[8]), x, double(iso.m[11]))));
+          const double cx = fma(iso.m[2], z, fma(iso.m[1], y, fma(iso.m[0], x, iso.m[3])));
+          const double cy = fma(iso.m[6], z, fma(iso.m[5], y, fma(iso.m[4], x, iso.m[7])));
+          const double cz = fma(iso.m[10], z, fma(iso.m[9], y, fma(iso.m[8], x, iso.m[11])));
           const double n2 = fma(cx, cx, fma(cy, cy, cz * cz));
           const double e1 = fma(fast.er, (fabs(x) + fabs(y)) + fabs(z), fast.et);
           if constexpr (MODEL == MODEL_EQUIRECT) {
@@ -779,7 +750,7 @@ __global__ __launch_bounds__(kThreads, nearest_min_waves(MODEL, std::is_same<rea
             const double b1 = (8.0 * e1) * m1;
             const double bd = fma(7e-15, m1, 4.0 * e1);
             // the cone
-            const double cf = double(cos_fov);
+            const double cf = cos_fov;
             const double g = fma(-(cf * fabs(cf)), n2, cz * fabs(cz));
             const bool fov_safe = fabs(g) > fma(16.0 * eps, n2, b1);
             const bool in_fov = g >= 0.0;
@@ -816,28 +787,28 @@ __global__ __launch_bounds__(kThreads, nearest_min_waves(MODEL, std::is_same<rea
             pys[k] = ins[k] ? row : 0;
           } else {
           const double rs = fast_rsq(n2);  // NaN for n2 == 0
-          const double dz = fma(cz, rs, -double(cos_fov));
+          const double dz = fma(cz, rs, -cos_fov);
           const bool fov_safe = fabs(dz) > fma(8.0 * e1, rs, 4e-14);
           const bool in_fov = !(dz < 0.0);
-          real u, v;
+          double u, v;
           double bu, bv;
           bool model_ok = true;  // (false: a rule of the model the bands do not cover -> exact tier)
           if constexpr (MODEL == MODEL_OMNIDIR) {
-            const OmnidirCore<real> kc = omnidir_core<real>(cam, real(cx), real(cy), real(cz));
-            project<MODEL, real, real, true>(cam, real(cx), real(cy), real(cz), u, v);  // (the same core: computed once after inlining)
-            bu = bv = fma(fast.A * e1, fabs(double(kc.iden)), fast.Bc);
+            const OmnidirCore<double> kc = omnidir_core<double>(cam, cx, cy, cz);
+            project<MODEL, double, double, true>(cam, cx, cy, cz, u, v);  // (the same core: computed once after inlining)
+            bu = bv = fma(fast.A * e1, fabs(kc.iden), fast.Bc);
             model_ok = n2 > 0.0;
           } else if constexpr (MODEL == MODEL_FISHEYE) {
-            const FisheyeCore<real> kc = fisheye_core<real>(cam, real(cx), real(cy), real(cz));
-            u = fma(cam.intr[0], kc.s * real(cx), cam.intr[2]);
-            v = fma(cam.intr[1], kc.s * real(cy), cam.intr[3]);
-            bu = bv = fma(e1, fma(fast.A, rs, fast.C * fabs(double(kc.s))), fast.Bc * ((fabs(double(u) - double(cam.intr[2])) + fabs(double(v) - double(cam.intr[3]))) + 1.0));
+            const FisheyeCore<double> kc = fisheye_core<double>(cam, cx, cy, cz);
+            u = fma(cam.intr[0], kc.s * cx, cam.intr[2]);
+            v = fma(cam.intr[1], kc.s * cy, cam.intr[3]);
+            bu = bv = fma(e1, fma(fast.A, rs, fast.C * fabs(kc.s)), fast.Bc * ((fabs(u - cam.intr[2]) + fabs(v - cam.intr[3])) + 1.0));
           } else {
-            project<MODEL, real, real, true>(cam, real(cx), real(cy), real(cz), u, v);
+            project<MODEL, double, double, true>(cam, cx, cy, cz, u, v);
             bu = bv = fma(fast.A * e1, fabs(fast_rcp(cz)), fast.Bc);
           }
-          const bool uv_safe = bool(int(model_ok) & int(fabs(double(u) - rint(double(u))) > bu) & int(fabs(double(v) - rint(double(v))) > bv));
-          const bool in_rng = bool(int(u > real(-1)) & int(u < fW) & int(v > real(-1)) & int(v < fH));
+          const bool uv_safe = bool(int(model_ok) & int(fabs(u - rint(u)) > bu) & int(fabs(v - rint(v)) > bv));
+          const bool in_rng = bool(int(u > -1.0) & int(u < fW) & int(v > -1.0) & int(v < fH));
           // decided: safely outside the cone (u, v do not matter), or safely inside it with every pixel decision safe
           const bool decided = bool(int(fov_safe) & (int(!in_fov) | int(uv_safe)));
           need[k] = bool(int(valid) & int(!decided));
@@ -1183,12 +1154,8 @@ __global__ __launch_bounds__(kEntropyThreads) void k_entropy_repl(
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this thread's stores have been performed at system scope
     __syncthreads();
     if (tid == 0) {
-#ifdef NID_SHARD_LIGHT_FENCE  // (A/B: every payload word above is a write-through system-scope store that has been waited for)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-#else
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
       const u64 word = block_flag(seq, Sg);
       for (int p = 0; p < n; p++) store_sys(&tab->flags[p][j], word);
     }
@@ -1288,99 +1255,76 @@ enum { TAP_COPIES = 0,   // gtile[(cell << cshift) + lane copy]: lane-private co
 // The point loop of the pass over ONE segment of the workgroup's chunk (`cnt` records from `recs`, all of column group
 // col0 / GW, whose G columns sit in gtile): accumulates M += gp p^T, gt += gp into acc[12].  `done` / `total`: the chunk's
 // progress (issue priority).
-template <int MODEL, typename Rec, typename real, int TAP, int kT, bool SPLIT>
+template <int MODEL, typename Rec, int TAP, int kT, bool SPLIT>
 __device__ __forceinline__ void spline_grad_loop(
-  const Rec* __restrict__ recs, uint32_t cnt, uint32_t col0, uint32_t done, uint32_t total, const uint8_t* __restrict__ img, int pitch, int W, int H, const PoseParams<real>& pose,
-  const CamParams<real>& cam, int B, int cshift, const double* gtile, double* acc, bool prio, uint32_t rec0 = 0) {
+  const Rec* __restrict__ recs, uint32_t cnt, uint32_t col0, uint32_t done, uint32_t total, const uint8_t* __restrict__ img, int pitch, int W, int H, const PoseParams<double>& pose,
+  const CamParams<double>& cam, int B, int cshift, const double* gtile, double* acc, bool prio) {
   const int tid = threadIdx.x;
   if (TAP == TAP_SINGLE) cshift = 0;
   const uint32_t cmask = (1u << cshift) - 1u;
-  const real fW = real(W), fH = real(H);
+  const double fW = double(W), fH = double(H);
   const uint32_t lane_copy = uint32_t(tid) & cmask;
 
   const char* rec_base = reinterpret_cast<const char*>(recs);  // uniform base + 32-bit byte offsets per lane
   auto batch = [&](uint32_t base, auto guarded) {  // GUARDED: see spline_hist_body
     constexpr bool GUARDED = decltype(guarded)::value;
     set_progress_priority(prio, done + base, total);
-    real xs[kUnroll], ys[kUnroll], zs[kUnroll];
+    double xs[kUnroll], ys[kUnroll], zs[kUnroll];
     uint32_t bins_[kUnroll];
     RawBatch<Rec, kUnroll> rb;
 #pragma unroll
     for (int k = 0; k < kUnroll; k++) rb.load(rec_base, (GUARDED ? min(base + uint32_t(k) * kT + tid, cnt - 1u) : base + uint32_t(k) * kT + tid) * uint32_t(sizeof(Rec)), k);
-#ifdef NID_EXP_HANDOFF
-    double2 huv[kUnroll];
 #pragma unroll
-    for (int k = 0; k < kUnroll; k++) huv[k] = g_uv_handoff[rec0 + (GUARDED ? min(base + uint32_t(k) * kT + tid, cnt - 1u) : base + uint32_t(k) * kT + tid)];
-#endif
-#pragma unroll
-    for (int k = 0; k < kUnroll; k++) rb.template get<real>(k, xs[k], ys[k], zs[k], bins_[k]);
+    for (int k = 0; k < kUnroll; k++) rb.get(k, xs[k], ys[k], zs[k], bins_[k]);
 #pragma unroll
     for (int k = 0; k < kUnroll; k++) {
       // (a branch-free body like k_spline_hist's was measured 15 % slower here: 173 VGPRs, 2 waves/SIMD)
       if (GUARDED && base + uint32_t(k) * kT + tid >= cnt) break;
-      const real x = xs[k], y = ys[k], z = zs[k];
-      real cx, cy, cz;
-      transform_fma<real>(pose, x, y, z, cx, cy, cz);
-      real uu, vv;
-      ProjCtx<real> ctx;
-      project_fwd<MODEL, real>(cam, cx, cy, cz, uu, vv, ctx);
-#ifdef NID_EXP_HANDOFF
-      uu = real(huv[k].x), vv = real(huv[k].y);  // the value half of project_fwd above is dead code now
-#endif
-      const bool in = (uu >= real(0)) && (uu < fW) && (vv >= real(0)) && (vv < fH);
+      const double x = xs[k], y = ys[k], z = zs[k];
+      double cx, cy, cz;
+      transform_fma<double>(pose, x, y, z, cx, cy, cz);
+      double uu, vv;
+      ProjCtx<double> ctx;
+      project_fwd<MODEL, double>(cam, cx, cy, cz, uu, vv, ctx);
+      const bool in = (uu >= 0.0) && (uu < fW) && (vv >= 0.0) && (vv < fH);
       if (in) {
         const int kx = int(uu), ky = int(vv);  // uu, vv >= 0 here: truncation is the floor knot
-        const real sx = m_abs(m_fract(uu)), sy = m_abs(m_fract(vv));  // |.| as in the histogram pass: identical fractions
-        real bx[4], by[4], dbx[4], dby[4];
-        bspline6<real>(sx, bx);
-        bspline6<real>(sy, by);
-        bspline_deriv2<real>(sx, dbx);
-        bspline_deriv2<real>(sy, dby);
+        const double sx = m_abs(m_fract(uu)), sy = m_abs(m_fract(vv));  // |.| as in the histogram pass: identical fractions
+        double bx[4], by[4], dbx[4], dby[4];
+        bspline6<double>(sx, bx);
+        bspline6<double>(sy, by);
+        bspline_deriv2<double>(sx, dbx);
+        bspline_deriv2<double>(sy, dby);
         typedef __attribute__((address_space(3))) const double lds_f64_t;
         const double* gcol = gtile + ((((bins_[k] - col0) * uint32_t(B)) << cshift) + lane_copy);
         uint32_t cols[4];
-#ifdef NID_EXP_GRAD_NOGATHER
-        cols[0] = uint32_t(kx) * 0x01010101u, cols[1] = cols[0] + 0x01010101u, cols[2] = uint32_t(ky) * 0x01010101u, cols[3] = cols[2] + 0x01010101u;
-#else
         load_patch(img, pitch, kx, ky, cols);
-#endif
-#ifdef NID_EXP_GRAD_PAD
-        {  // experiment: NID_EXP_GRAD_PAD independent fp64 fmas per point (marginal cost of a VALU instruction)
-          double pa = double(sx), pb = double(sy), pc = double(uu), pd = double(vv);
-#pragma unroll
-          for (int q = 0; q < NID_EXP_GRAD_PAD / 4; q++) {
-            pa = fma(pa, 0.999, 0.25), pb = fma(pb, 0.999, 0.25), pc = fma(pc, 0.999, 0.25), pd = fma(pd, 0.999, 0.25);
-          }
-          acc[11] += (pa + pb + pc + pd) * 1e-300;
-        }
-#endif
-        real gx = real(0), gy = real(0);
+        double gx = 0.0, gy = 0.0;
 #pragma unroll
         for (int b = 0; b < 4; b++) {
-          real sa = real(0), sb = real(0);
+          double sa = 0.0, sb = 0.0;
 #pragma unroll
           for (int a = 0; a < 4; a++) {
             const uint32_t r = (cols[a] >> (8 * b)) & 0xffu;
-            const real g = TAP == TAP_SINGLE ? real(*(lds_f64_t*)(uintptr_t)(r << 3)) : real(gcol[r << cshift]);
+            const double g = TAP == TAP_SINGLE ? *(lds_f64_t*)(uintptr_t)(r << 3) : gcol[r << cshift];
             sa = fma(g, dbx[a], sa);
             sb = fma(g, bx[a], sb);
           }
           gx = fma(sa, by[b], gx);
           gy = fma(sb, dby[b], gy);
         }
-        real gpr[3];
-        project_bwd<MODEL, real>(cam, ctx, gx, gy, gpr);
-        const double gp0 = double(gpr[0]), gp1 = double(gpr[1]), gp2 = double(gpr[2]);
-        const double dx = double(x), dy = double(y), dz = double(z);
-        acc[0] = fma(gp0, dx, acc[0]);
-        acc[1] = fma(gp0, dy, acc[1]);
-        acc[2] = fma(gp0, dz, acc[2]);
-        acc[3] = fma(gp1, dx, acc[3]);
-        acc[4] = fma(gp1, dy, acc[4]);
-        acc[5] = fma(gp1, dz, acc[5]);
-        acc[6] = fma(gp2, dx, acc[6]);
-        acc[7] = fma(gp2, dy, acc[7]);
-        acc[8] = fma(gp2, dz, acc[8]);
+        double gpr[3];
+        project_bwd<MODEL, double>(cam, ctx, gx, gy, gpr);
+        const double gp0 = gpr[0], gp1 = gpr[1], gp2 = gpr[2];
+        acc[0] = fma(gp0, x, acc[0]);
+        acc[1] = fma(gp0, y, acc[1]);
+        acc[2] = fma(gp0, z, acc[2]);
+        acc[3] = fma(gp1, x, acc[3]);
+        acc[4] = fma(gp1, y, acc[4]);
+        acc[5] = fma(gp1, z, acc[5]);
+        acc[6] = fma(gp2, x, acc[6]);
+        acc[7] = fma(gp2, y, acc[7]);
+        acc[8] = fma(gp2, z, acc[8]);
         acc[9] += gp0;
         acc[10] += gp1;
         acc[11] += gp2;
@@ -1388,15 +1332,10 @@ __device__ __forceinline__ void spline_grad_loop(
     }
   };
   // every full batch without the bounds checks, the last one with them: 18 of ~920 instructions per batch less, 75.3-75.8 ->
-  // 74.8-75.0 us on cfg 2 (profiles/archive/r04g_variants.txt; -DNID_GRAD_ALWAYS_GUARDED: the single loop)
+  // 74.8-75.0 us on cfg 2 (profiles/archive/r04g_variants.txt)
   // (SPLIT = false: the looped kernel instantiations, which have no registers to spare for a second copy of the body)
-#ifdef NID_GRAD_ALWAYS_GUARDED
-  constexpr bool kSplit = false;
-#else
-  constexpr bool kSplit = SPLIT;
-#endif
   uint32_t base = 0;
-  if constexpr (kSplit)
+  if constexpr (SPLIT)
     for (; base + uint32_t(kT * kUnroll) <= cnt; base += kT * kUnroll) batch(base, std::false_type());
   for (; base < cnt; base += kT * kUnroll) batch(base, std::true_type());
 }
@@ -1409,24 +1348,11 @@ __device__ __forceinline__ void spline_grad_loop(
 // stores its 12 accumulators ([12][kT], conflict-free), 12 x 16 threads each add 16 of them (stride 16: conflict-free reads)
 // and finish inside their DPP row of 16 lanes (row_shr 1 / 2 / 4 / 8): ~60 instructions per thread, a fixed association like
 // before.  `scratch`: 12 * kT doubles of LDS that may alias the G tile (dead once every wave has left the point loop: hence the
-// barrier up front).  -DNID_GRAD_REDUCE_DPP restores the round-4 reduction (A/B).
+// barrier up front).
 constexpr int kGradScratchDoubles = 12 * kThreads;
 template <int kT>
-__device__ __forceinline__ void grad_reduce_store(const double* acc, double* s_red, double* scratch, double* partials, unsigned int my_block, unsigned int my_blocks) {
+__device__ __forceinline__ void grad_reduce_store(const double* acc, double* scratch, double* partials, unsigned int my_block, unsigned int my_blocks) {
   const int tid = threadIdx.x;
-#ifdef NID_GRAD_REDUCE_DPP
-#pragma unroll
-  for (int k = 0; k < 12; k++) {
-    const double t = wave_sum(acc[k]);
-    if ((tid & 63) == 0) s_red[(tid >> 6) * 12 + k] = t;
-  }
-  __syncthreads();
-  if (tid < 12) {
-    double t = 0.0;
-    for (int w = 0; w < kT / 64; w++) t += s_red[w * 12 + tid];
-    __hip_atomic_store(&partials[size_t(tid) * my_blocks + my_block], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-#else
   static_assert(kT == 256, "12 accumulators x 16 lanes = 192 threads of the workgroup's 256");
   __syncthreads();  // every wave has left the point loop: the G tile under `scratch` is dead
 #pragma unroll
@@ -1443,8 +1369,6 @@ __device__ __forceinline__ void grad_reduce_store(const double* acc, double* s_r
     t += dpp_move<0x118, 0xf, true>(t);
     if (j == 15) __hip_atomic_store(&partials[size_t(k) * my_blocks + my_block], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  (void)s_red;
-#endif
 }
 
 // (struct GradTail, what the gradient kernel needs to run the entropy tail itself: nid_multi.hpp, shared with the host)
@@ -1573,19 +1497,15 @@ constexpr int grad_min_waves(int model, bool seg = false, bool rec32 = false) { 
 // the region at the start of the gradient kernel's LDS: the G tile during the point loop, the reduction's scratch after it
 __host__ __device__ __forceinline__ size_t grad_tile_region_bytes(int B, int GW, int cshift) {
   const size_t tile = GW == 1 ? size_t(B) * 8 : (size_t(GW) * size_t(B) * 8 << cshift);
-#ifdef NID_GRAD_REDUCE_DPP
-  return tile;
-#else
   return tile > size_t(12 * 256 * 8) ? tile : size_t(12 * 256 * 8);
-#endif
 }
 __host__ __device__ __forceinline__ size_t spline_grad_lds_bytes(int B, int GW, int cshift, bool seg) {
   return grad_tile_region_bytes(B, GW, cshift) + size_t(kWaves) * 12 * 8 + 256 * 8 + 16 + 32 + (seg && GW == 1 ? size_t(kMaxSegs - 1) * size_t(B) * 8 : 0);
 }
-template <int MODEL, typename Rec, typename real, bool GW1, bool MULTI, bool SEG>
+template <int MODEL, typename Rec, bool GW1, bool MULTI, bool SEG>
 __global__ __launch_bounds__(kThreads, grad_min_waves(MODEL, SEG, sizeof(Rec) == sizeof(Rec32))) void k_spline_grad(
-  const Rec* __restrict__ pts, const Chunk* __restrict__ chunks, const uint32_t* __restrict__ gend, const uint8_t* __restrict__ img, int pitch, int W, int H, PoseParams<real> pose,
-  CamParams<real> cam, int B, int GW, int cshift, double inv_unit, const u64* __restrict__ hist, const double* __restrict__ phi_q, const EntropyScalars* __restrict__ scal, GradTail gt,
+  const Rec* __restrict__ pts, const Chunk* __restrict__ chunks, const uint32_t* __restrict__ gend, const uint8_t* __restrict__ img, int pitch, int W, int H, PoseParams<double> pose,
+  CamParams<double> cam, int B, int GW, int cshift, double inv_unit, const u64* __restrict__ hist, const double* __restrict__ phi_q, const EntropyScalars* __restrict__ scal, GradTail gt,
   double* partials, unsigned int nslots, double qx, double qy, double qz, double qw, double* out, double* out_host, double tag, unsigned int* counter, int prio,
   const MultiEntry* __restrict__ multi, typename multi_dyn_of<MULTI>::type dyn) {
   static_assert(!SEG || GW1, "a chunk runs across column groups only in the single-column kernels (the host builds one-segment tables otherwise)");
@@ -1687,10 +1607,10 @@ __global__ __launch_bounds__(kThreads, grad_min_waves(MODEL, SEG, sizeof(Rec) ==
       acc[k] = zero;
     }
     const uint32_t seg_end = SEG ? seg.seg_end() : seg.end;
-    spline_grad_loop<MODEL, Rec, real, GW1 ? TAP_SINGLE : TAP_COPIES, kThreads, !SEG>(pts + seg.pos, seg_end - seg.pos, seg.g * uint32_t(GW), seg.pos - ch.start, ch.count, img, pitch, W, H, pose,
-                                                                               cam, B, cshift, gtile, acc, prio != 0, seg.pos);
+    spline_grad_loop<MODEL, Rec, GW1 ? TAP_SINGLE : TAP_COPIES, kThreads, !SEG>(pts + seg.pos, seg_end - seg.pos, seg.g * uint32_t(GW), seg.pos - ch.start, ch.count, img, pitch, W, H, pose,
+                                                                               cam, B, cshift, gtile, acc, prio != 0);
     stamp_stage(3);
-    grad_reduce_store<kThreads>(acc, s_red, gtile, partials, slot, nslots);
+    grad_reduce_store<kThreads>(acc, gtile, partials, slot, nslots);
     stamp_stage(4);
     if (!SEG || !seg.advance(seg_end)) break;
     slot++;
@@ -1716,21 +1636,21 @@ __global__ __launch_bounds__(kThreads) void k_grad_final(const double* partials,
 #endif  // NID_FINAL_KERNEL
 
 // GenericCameraBase::project on the device (test / utility path): uv and the 2x3 Jacobian
-template <int MODEL, typename real>
-__global__ void k_project(const double* __restrict__ p3, long long n, CamParams<real> cam, double* __restrict__ uv, double* __restrict__ jac) {
+template <int MODEL>
+__global__ void k_project(const double* __restrict__ p3, long long n, CamParams<double> cam, double* __restrict__ uv, double* __restrict__ jac) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  real u, v, du[3], dv[3];
-  project_jac<MODEL, real>(cam, real(p3[3 * i]), real(p3[3 * i + 1]), real(p3[3 * i + 2]), u, v, du, dv);
-  uv[2 * i] = double(u);
-  uv[2 * i + 1] = double(v);
+  double u, v, du[3], dv[3];
+  project_jac<MODEL, double>(cam, p3[3 * i], p3[3 * i + 1], p3[3 * i + 2], u, v, du, dv);
+  uv[2 * i] = u;
+  uv[2 * i + 1] = v;
   if (jac) {
-    jac[6 * i + 0] = double(du[0]);
-    jac[6 * i + 1] = double(du[1]);
-    jac[6 * i + 2] = double(du[2]);
-    jac[6 * i + 3] = double(dv[0]);
-    jac[6 * i + 4] = double(dv[1]);
-    jac[6 * i + 5] = double(dv[2]);
+    jac[6 * i + 0] = du[0];
+    jac[6 * i + 1] = du[1];
+    jac[6 * i + 2] = du[2];
+    jac[6 * i + 3] = dv[0];
+    jac[6 * i + 4] = dv[1];
+    jac[6 * i + 5] = dv[2];
   }
 }
 

@@ -1,4 +1,4 @@
-// double-precision SPLINE (NIDCost) kernels + projection utility.  Built with -ffp-contract=off like every other
+// SPLINE (NIDCost) kernels + projection utility.  Built with -ffp-contract=off like every other
 // translation unit (csrc/Makefile): the fusions wanted are explicit fma calls, so a point gets the same arithmetic
 // whichever unrolled slot / chunk / GPU processes it.
 #include "nid_launch_impl.hpp"
@@ -20,14 +20,10 @@ hipError_t launch_project(int model, const double* intr, const double* dist, con
   const CamParams<double> cam = make_cam(model, intr, dist);
   const unsigned grid = unsigned((n + 255) / 256);
   return with_model(model, hipErrorInvalidValue, [&](auto M) {
-    hipLaunchKernelGGL((k_project<M, double>), dim3(grid), dim3(256), 0, stream, p3, n, cam, uv, jac);
+    hipLaunchKernelGGL(k_project<M>, dim3(grid), dim3(256), 0, stream, p3, n, cam, uv, jac);
     return hipGetLastError();
   });
 }
-
-#ifdef NID_EXP_HANDOFF
-hipError_t set_handoff_buffer(void* p) { return hipMemcpyToSymbol(HIP_SYMBOL(g_uv_handoff), &p, sizeof(p)); }
-#endif
 
 // the same projection code on the HOST (nid_device.hpp's scalar math is __host__ __device__): for callers that project a
 // handful of points at a time -- estimate_camera_fov inverts the projection at three pixels with NelderMead<2>, ~240 probes

@@ -1,6 +1,6 @@
-// double-precision NEAREST (CostCalculatorNID) kernels.  Build with -ffp-contract=off: the arithmetic
-// follows the reference's expression tree, so +,-,*,/,sqrt are bit-identical to the CPU's and the
-// integer histogram is exactly reproducible.
+// NEAREST (CostCalculatorNID) kernels, view culling and the render kernels.  Built with -ffp-contract=off like every
+// other translation unit (csrc/Makefile): the NEAREST exact tier follows the reference's expression tree, so its
+// +,-,*,/,sqrt are bit-identical to the CPU's and the integer histogram is exactly reproducible.
 #include "nid_launch_impl.hpp"
 #include "nid_cull_kernels.hpp"
 #include "nid_render_kernels.hpp"

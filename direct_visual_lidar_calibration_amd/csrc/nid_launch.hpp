@@ -80,9 +80,6 @@ hipError_t launch_spline_fused(const PassArgs& a, const FusedArgs& f);
 int occupancy_spline_fused(const PassArgs& a, const FusedArgs& f);  // workgroups of that instantiation per CU (0 on error)
 hipError_t launch_project(int model, const double* intr, const double* dist, const double* p3, long long n, double* uv, double* jac, hipStream_t stream);
 
-#ifdef NID_EXP_HANDOFF
-hipError_t set_handoff_buffer(void* p);  // nid_kernels_f64.hip (experiment)
-#endif
 // the same scalar projection code run on the host (nid_kernels_f64.hip): host arrays, fp64, 0 = ok
 int project_host(int model, const double* intr, const double* dist, const double* p3, long long n, double* uv, double* jac);
 // vlcal::estimate_direction (estimate_fov.cpp:17-34) over project_host: the bearing of pixel (pu, pv) by NelderMead<2> (nidreg_pose.hip)

@@ -74,7 +74,7 @@ static hipError_t spline_hist_rec(const PassArgs& a, int* occ) {
     return with_bool(a.wide, [&](auto WIDE) {  // B = 256, GW = 1, 32 copies, 512 threads (see k_spline_hist)
       return with_bool(!occ && a.seg, [&](auto SEG) {  // the table has chunks that run across column-group boundaries (nid_kernels.hpp Segments)
         return with_bool(!occ && a.multi, [&](auto MULTI) {
-          return launch_chunks(k_spline_hist<M, Rec, double, WIDE, MULTI, SEG>, WIDE ? kWideThreads : kThreads, a.lds_hist, a, occ, static_cast<const Rec*>(a.pts), a.chunks, a.gend,
+          return launch_chunks(k_spline_hist<M, Rec, WIDE, MULTI, SEG>, WIDE ? kWideThreads : kThreads, a.lds_hist, a, occ, static_cast<const Rec*>(a.pts), a.chunks, a.gend,
                                a.img, a.pitch, a.W, a.H, pose, cam, a.B, a.GW, a.cshift, a.magic, a.hist, a.prio, a.multi, dyn_of<MULTI>(a));
         });
       });
@@ -93,7 +93,7 @@ static hipError_t spline_grad_rec(const PassArgs& a, int* occ) {
           if constexpr (SEG && !GW1) {
             return hipErrorInvalidValue;  // multi-segment tables are built for the single-column kernels only
           } else {
-            return launch_chunks(k_spline_grad<M, Rec, double, GW1, MULTI, SEG>, kThreads, a.lds_grad, a, occ, static_cast<const Rec*>(a.pts), a.chunks, a.gend, a.img, a.pitch, a.W,
+            return launch_chunks(k_spline_grad<M, Rec, GW1, MULTI, SEG>, kThreads, a.lds_grad, a, occ, static_cast<const Rec*>(a.pts), a.chunks, a.gend, a.img, a.pitch, a.W,
                                  a.H, pose, cam, a.B, a.GW, a.cshift, a.inv_unit, a.hist, a.phi_q, a.scal, a.gt, a.partials, unsigned(a.nslots), a.q[0], a.q[1], a.q[2], a.q[3], a.out,
                                  a.out_host, a.tag, a.counter, a.prio, a.multi, dyn_of<MULTI>(a));
           }
@@ -110,7 +110,7 @@ static hipError_t nearest_hist_rec(const PassArgs& a, int* occ) {
   return with_model(a.model, hipErrorInvalidValue, [&](auto M) {
     return with_bool(!occ && a.seg, [&](auto SEG) {
       return with_bool(!occ && a.multi, [&](auto MULTI) {
-        return launch_chunks(k_nearest_hist<M, Rec, double, MULTI, SEG>, kThreads, a.lds_hist, a, occ, static_cast<const Rec*>(a.pts), a.chunks, a.gend, a.img, a.pitch, a.W, a.H, iso,
+        return launch_chunks(k_nearest_hist<M, Rec, MULTI, SEG>, kThreads, a.lds_hist, a, occ, static_cast<const Rec*>(a.pts), a.chunks, a.gend, a.img, a.pitch, a.W, a.H, iso,
                              cam, a.B, a.GW, a.cshift, a.cos_fov, a.nfast, a.hist, a.multi, dyn_of<MULTI>(a));
       });
     });

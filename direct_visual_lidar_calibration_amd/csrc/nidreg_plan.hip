@@ -623,15 +623,6 @@ int create_impl(const nidreg_desc* d, const nidreg_cloud* cloud, const double* T
   if (rc == NIDREG_OK) rc = plan_chunk_tables(h.get(), dd);
   if (rc == NIDREG_OK) rc = build_equirect_tables(h.get());
   if (rc) return rc;
-#ifdef NID_EXP_HANDOFF
-  {  // EXPERIMENT: the (u, v) hand-off buffer of the process' one handle (leaked at destruction: an experiment build)
-    void* uvb = nullptr;
-    const int64_t N = h->num_points;
-    HIP_TRY(hipMalloc(&uvb, size_t(std::max<int64_t>(N, 1)) * 16 + 64));
-    HIP_TRY(hipMemset(uvb, 0, size_t(std::max<int64_t>(N, 1)) * 16 + 64));
-    HIP_TRY(set_handoff_buffer(uvb));
-  }
-#endif
   rc = alloc_eval_state(h.get(), dd, opts.shard);
   if (rc) return rc;
   *out = h.release();

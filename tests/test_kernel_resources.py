@@ -43,8 +43,8 @@ def _find(meta, fragment):
 
 def test_headline_spline_kernels_fit_four_waves_per_simd(kernel_metadata):
     _, meta = kernel_metadata
-    # k_spline_hist<plumb_bob, Rec32, double, WIDE, single / multi pair>, k_spline_grad<plumb_bob, Rec32, double, GW1, ...>
-    for fragment in ("k_spline_histILi0ENS_5Rec32EdLb1E", "k_spline_gradILi0ENS_5Rec32EdLb1E"):
+    # k_spline_hist<plumb_bob, Rec32, WIDE, single / multi pair>, k_spline_grad<plumb_bob, Rec32, GW1, ...>
+    for fragment in ("k_spline_histILi0ENS_5Rec32ELb1E", "k_spline_gradILi0ENS_5Rec32ELb1E"):
         for name, m in _find(meta, fragment).items():
             assert m["vgpr"] <= 128, (name, m)
             assert m["vgpr_spill"] == 0 and m["scratch"] == 0, (name, m)
@@ -54,7 +54,7 @@ def test_no_spline_kernel_uses_scratch(kernel_metadata):
     _, meta = kernel_metadata
     for name, m in {**_find(meta, "k_spline_hist"), **_find(meta, "k_spline_grad")}.items():
         assert m["vgpr"] <= 168, (name, m)  # at least three waves per SIMD for every camera model
-        looped = re.search(r"Lb1EEEv", name) is not None  # template <MODEL, Rec, real, WIDE | GW1, MULTI, SEG>: SEG = the segment loop
+        looped = re.search(r"Lb1EEEv", name) is not None  # template <MODEL, Rec, WIDE | GW1, MULTI, SEG>: SEG = the segment loop
         if "k_spline_gradILi4E" in name:
             # the `atan` model (generic Dual3 forward mode) is held at three waves per SIMD by its launch bounds and may park a
             # few registers in scratch outside the point loop
@@ -89,13 +89,13 @@ def test_every_model_but_atan_fits_four_waves_per_simd_in_the_gradient_pass(kern
     """Round 3: fast_atan2 from a table took the fisheye / equirectangular gradient kernels from 154-162 to <= 128 VGPRs."""
     _, meta = kernel_metadata
     for name, m in _find(meta, "k_spline_grad").items():
-        if "k_spline_gradILi4E" not in name and "Rec32EdLb1E" in name:
+        if "k_spline_gradILi4E" not in name and "Rec32ELb1E" in name:
             assert m["vgpr"] <= 128, (name, m)
 
 
 def test_wave_sums_use_dpp_not_the_lds_crossbar(kernel_metadata):
     text, _ = kernel_metadata
-    start = text.index("k_spline_gradILi0ENS_5Rec32EdLb1ELb0ELb0E")
+    start = text.index("k_spline_gradILi0ENS_5Rec32ELb1ELb0ELb0E")
     body = text[start:text.index(".Lfunc_end", start)]
     assert "row_bcast:31" in body and "ds_bpermute" not in body
 
@@ -103,7 +103,7 @@ def test_wave_sums_use_dpp_not_the_lds_crossbar(kernel_metadata):
 def test_wide_histogram_kernel_keeps_the_tile_at_lds_address_zero(kernel_metadata):
     # the WIDE kernel builds a tap's LDS address with one v_perm_b32 on the assumption that its dynamic tile starts at 0
     _, meta = kernel_metadata
-    for name, m in _find(meta, "k_spline_histILi0ENS_5Rec32EdLb1E").items():
+    for name, m in _find(meta, "k_spline_histILi0ENS_5Rec32ELb1E").items():
         assert m["lds_static"] == 0, (name, m)
 
 

@@ -94,7 +94,7 @@ int main(int argc, char** argv) {
   cam.dist[0] = -0.04, cam.dist[1] = 0.08, cam.dist[2] = 1e-4, cam.dist[3] = -3e-4, cam.dist[4] = -0.04;
   const int frac = 38;
   const double dn = std::ldexp(1.0, frac - 1074);
-  auto k = k_spline_hist<MODEL_PLUMB_BOB, Rec32, double, true, false, false>;
+  auto k = k_spline_hist<MODEL_PLUMB_BOB, Rec32, true, false, false>;
   const size_t lds = (size_t(B) * 8 << kWideShift) + 8 + 16;
   CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
   hipEvent_t e0, e1;
