@@ -176,7 +176,9 @@ __device__ __forceinline__ void grad_final_body(const double* partials, int nblo
   for (int k = 0; k < 12; k++) acc[k] = 0.0;
   // (Round 6 tried four rounds of these 12 loads in flight per thread -- the full round's 1024 partials take four dependent trips to
   // the coherence point here --: the finalising workgroup's stage 4.9 -> 4.2 us at 10M points, the gradient kernel 73.9 -> 73.4 us,
-  // and +1 us on a 100k-point evaluation (the predicated rounds still issue); profiles/r06_experiments.md section 5.  One round per trip.)
+  // and +1 us on a 100k-point evaluation (the predicated rounds still issue); profiles/r06_experiments.md section 5.  One round per trip.
+  // Tried again behind a template parameter, for the single-column kernels without segments only: the stage 4.95 -> 4.70 us, but the
+  // same kernel's point loop, whose source did not change, 59.1 -> 59.8 us at the median; profiles/r07_serial_stages.md.)
   for (int b = tid; b < nblocks; b += kT) {
 #pragma unroll
     for (int k = 0; k < 12; k++) acc[k] += COH ? __hip_atomic_load(&partials[size_t(k) * nblocks + b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : partials[size_t(k) * nblocks + b];
@@ -521,13 +523,35 @@ __device__ __forceinline__ void spline_hist_body(
     stamp_stage(2);
 
     // flush the tile: contiguous in the [bin_points][bin_image] device layout
+    // Column sums: integers, so any grouping gives the same word.  A workgroup with ONE column (WIDE; the generic kernel at GW = 1)
+    // sums per thread, then over the wave (DPP), and adds once per wave -- one LDS atomic per non-zero cell on a single address before.
     u64* dst = hist + size_t(seg.g) * size_t(tile_n);
-    for (int k = tid; k < tile_n; k += kT) {
+    if constexpr (WIDE && kT == 2 * 256) {
+      // two threads per cell, 16 of its 32 copies each: lanes 2k / 2k + 1 start 16 copies apart, so 32 consecutive lanes still read 32
+      // different copies (bank pairs) in every step; the halves meet by one DPP swap inside the lane pair
+      const uint32_t k = uint32_t(tid) >> 1, half = uint32_t(tid) & 1u;
       u64 vv = 0;
-      for (uint32_t j = 0; j <= cmask; j++) vv += tile[(uint32_t(k) << cshift) + ((j + uint32_t(k)) & cmask)];  // rotated: conflict-free reads
-      if (vv) {
-        atomicAdd(&dst[k], vv);
-        atomicAdd(&s_colsum[k / B], vv);
+      for (uint32_t j = 0; j < 16; j++) vv += tile[(k << kWideShift) + ((j + 16u * half + k) & 31u)];
+      vv += u64(dpp_move_i64<0xB1, 0xf, false>((long long)vv));  // quad_perm:[1,0,3,2]
+      const u64 mine = half == 0 ? vv : 0;
+      if (mine) atomicAdd(&dst[k], mine);
+      const u64 wsum = u64(wave_sum((long long)mine));
+      if ((tid & 63) == 0 && wsum) atomicAdd(&s_colsum[0], wsum);
+    } else {
+      const bool one_col = GW == 1;  // (uniform)
+      u64 csum = 0;
+      for (int k = tid; k < tile_n; k += kT) {
+        u64 vv = 0;
+        for (uint32_t j = 0; j <= cmask; j++) vv += tile[(uint32_t(k) << cshift) + ((j + uint32_t(k)) & cmask)];  // rotated: conflict-free reads
+        if (vv) {
+          atomicAdd(&dst[k], vv);
+          if (one_col) csum += vv;
+          else atomicAdd(&s_colsum[k / B], vv);
+        }
+      }
+      if (one_col) {
+        const u64 wsum = u64(wave_sum((long long)csum));
+        if ((tid & 63) == 0 && wsum) atomicAdd(&s_colsum[0], wsum);
       }
     }
     __syncthreads();
@@ -1584,7 +1608,10 @@ __global__ __launch_bounds__(kThreads, grad_min_waves(MODEL, SEG, sizeof(Rec) ==
     // The G column(s) of EVERY segment of the chunk are built here, before the point loops: the first one in place, the others
     // into the staging area, from where a boundary costs one LDS copy.  (Rebuilding inside the segment loop let the compiler
     // hoist the logarithm's constants out of that loop and keep them through the point loop: 167 VGPRs; a call that is not
-    // inlined pinned the loop's values to the callee-saved registers: 145.)
+    // inlined pinned the loop's values to the callee-saved registers: 145.  Also measured: phi(h / S) of the own column's cells computed
+    // alongside the tail -- the cells loaded with the tail's loads, the logarithm / division chain in the row chain's straight-line
+    // code -- and only the last four operations here: the prologue's median unchanged (3.3-3.5 us either way), its slowest workgroup
+    // 6.3 -> 7.0-8.7 us; profiles/r07_serial_stages.md.)
     Segments sg(gend, ch);
     build_gtile(hist, sg.g, B, GW, cshift, scale, coefA, coefB, phi_q, gtile);
     if constexpr (SEG) {
