@@ -84,6 +84,7 @@ EXPORTS = [
     "nidreg_jpeg_info", "nidreg_jpeg_coefficients", "nidreg_jpeg_decode_gray", "nidreg_jpeg_get_timing",
     "nidreg_image_to_mono8", "nidreg_image_get_timing",
     "nidreg_velodyne_decode", "nidreg_velodyne_get_timing",
+    "nidreg_ouster_decode", "nidreg_ouster_get_timing",
     "nidreg_draw",
     "nidreg_mask_create", "nidreg_mask_get", "nidreg_mask_destroy", "nidreg_cloud_select", "nidreg_cloud_select_counts", "nidreg_cloud_size", "nidreg_cloud_get",
 ]
@@ -201,6 +202,9 @@ def load():
     lib.nidreg_velodyne_decode.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                            c_float_p, c_int32_p]
     lib.nidreg_velodyne_get_timing.argtypes = [c_double_p]
+    lib.nidreg_ouster_decode.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,
+                                         ctypes.c_double, c_double_p, ctypes.c_uint64, ctypes.c_void_p, c_int32_p]
+    lib.nidreg_ouster_get_timing.argtypes = [c_double_p]
     lib.nidreg_draw.argtypes = [ctypes.c_int, c_uint8_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_uint8_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, c_int32_p, c_uint8_p]
     lib.nidreg_mask_create.argtypes = [ctypes.c_int, c_uint8_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
     lib.nidreg_mask_get.argtypes = [ctypes.c_void_p, c_uint8_p, ctypes.c_int64]

@@ -1,4 +1,4 @@
-"""The two LiDAR message types that are recorded INSTEAD of ``sensor_msgs/PointCloud2``, read without the vendor drivers: every one
+"""The three LiDAR message types that are recorded INSTEAD of ``sensor_msgs/PointCloud2``, read without the vendor drivers: every one
 becomes a ``rosbag1.PointCloud2`` tuple, which is all the bag pipeline (``preprocess_ros1.run``) knows.
 
 ==========================================================  =====================================================================
@@ -8,15 +8,27 @@ becomes a ``rosbag1.PointCloud2`` tuple, which is all the bag pipeline (``prepro
                                                              ``velodyne_pointcloud`` publishes, no-return records as NaN
 ``livox_ros_driver(2)/CustomMsg`` (``.../msg/CustomMsg``)    a view of the message's own 19-byte (CDR: 20-byte) point records under
                                                              the fields t (uint32 ns), x, y, z, reflectivity, tag, line: no kernel
+``ouster_ros/PacketMsg`` (``ouster_msgs/msg/PacketMsg``,     one UDP packet of an Ouster sensor a message -- a 64th or 128th of a turn --,
+``ouster_sensor_msgs/msg/PacketMsg``)                        batched into scans by ``frame_id`` (``batch_points``) and decoded on the GPU
+                                                             (``nidreg_ouster_decode``) into 32-byte records x, y, z, intensity, t,
+                                                             reflectivity, ring, ambient, range in PACKET order (the driver's cloud is
+                                                             the destaggered H x W image); the geometry comes from the sensor's
+                                                             metadata JSON (``--ouster_metadata``, ``--ouster_frame``)
 ==========================================================  =====================================================================
 
 Both layouts, the packet rules and the two laser tables below are restated from the message definitions, the VLP-16 / HDL-32E manuals
 and ``velodyne_pointcloud``'s ``rawdata.cc`` from memory: they are UNPINNED against ``velodyne_pointcloud``, ``livox_ros_driver`` and real
 recordings.  Out of scope, refused by name where they can be told: dual-return packets, VLP-32C, VLS-128, HDL-64E (the two-point
-calibration), Ouster and Hesai packets.  The Livox ``tag`` (noise / return number), ``line``, ``lidar_id`` and ``timebase`` are carried or
+calibration) and Hesai packets.  The Livox ``tag`` (noise / return number), ``line``, ``lidar_id`` and ``timebase`` are carried or
 dropped, never interpreted.
+
+The Ouster packet layouts (LEGACY, RNG19_RFL8_SIG16_NIR16, RNG15_RFL8_NIR8), the metadata keys and the beam geometry are restated from
+the sensor's software manual and the SDK's field tables from memory as well: UNPINNED against ``ouster_ros``, the Ouster SDK and real
+recordings.  Refused by name: the dual-return and FUSA profiles.  Not read: the IMU packets (same message type; a buffer of another
+length than the profile's packet is refused), the packet header's and footer's other fields, ``pixel_shift_by_row``.
 """
 import ctypes
+import json
 import math
 from collections import namedtuple
 
@@ -43,10 +55,11 @@ LIVOX_FIELDS = [PointField("t", 0, UINT32, 1), PointField("x", 4, FLOAT32, 1), P
 
 
 def points_kind(type_name):
-    """``"PointCloud2"``, ``"VelodyneScan"`` or ``"CustomMsg"`` for a connection type this module turns into a cloud, else ``None``"""
+    """``"PointCloud2"``, ``"VelodyneScan"``, ``"CustomMsg"`` or ``"PacketMsg"`` for a connection type this module turns into a cloud, else
+    ``None``"""
     if type_name.endswith("/PointCloud2") or type_name == "PointCloud2":
         return "PointCloud2"
-    for kind in ("VelodyneScan", "CustomMsg"):
+    for kind in ("VelodyneScan", "CustomMsg", "PacketMsg"):
         if type_name.endswith("/" + kind) or type_name == kind:
             return kind
     return None
@@ -181,9 +194,10 @@ def load_calibration(path):
 
 class LidarOptions:
     """``--lidar_model`` and ``--velodyne_calibration`` of one run: the calibration file is read once, here; with ``auto`` the model is
-    fixed by the first packet decoded."""
+    fixed by the first packet decoded.  ``ouster``: the ``OusterInfo`` of ``--ouster_metadata`` / ``--ouster_frame`` for a PacketMsg topic."""
 
-    def __init__(self, lidar_model="auto", velodyne_calibration=None):
+    def __init__(self, lidar_model="auto", velodyne_calibration=None, ouster=None):
+        self.ouster = ouster  # the ``OusterInfo`` of a PacketMsg topic (``--ouster_metadata``, ``--ouster_frame``), else ``None``
         if lidar_model != "auto" and lidar_model not in LIDAR_MODELS:
             raise ValueError(f"error: --lidar_model {lidar_model}: auto, vlp16 and hdl32e are the options")
         self.model = None
@@ -198,6 +212,227 @@ class LidarOptions:
         if self.model is None:
             self.model = model_from_product_id(product_id)
         return self.model
+
+
+# ---------------------------------------------------------------------------------------------- Ouster: message, metadata, batching
+OUSTER_PROFILES = {"LEGACY": 0, "RNG19_RFL8_SIG16_NIR16": 1, "RNG15_RFL8_NIR8": 2}  # NIDREG_OUSTER_* of include/nidreg.h
+OUSTER_MAX_PACKETS = 4096  # nidreg_ouster_decode's limit
+OUSTER_RECORD_BYTES = 32
+OUSTER_FRAMES = ("sensor", "lidar")
+OUSTER_GROUPS = ("beam_intrinsics", "lidar_data_format", "data_format", "lidar_intrinsics", "config_params")
+UINT16 = 4  # sensor_msgs/PointField
+OUSTER_FIELDS = [PointField("x", 0, FLOAT32, 1), PointField("y", 4, FLOAT32, 1), PointField("z", 8, FLOAT32, 1), PointField("intensity", 12, FLOAT32, 1),
+                 PointField("t", 16, UINT32, 1), PointField("reflectivity", 20, UINT16, 1), PointField("ring", 22, UINT16, 1), PointField("ambient", 24, UINT16, 1),
+                 PointField("range", 28, UINT32, 1)]
+
+# profile: the index of OUSTER_PROFILES; column_table (W, 2), beam_table (H, 4), transform12 (12,): nidreg_ouster_decode's arguments
+OusterInfo = namedtuple("OusterInfo", "profile_name profile H W C packet_size column_table beam_table n_mm transform12 frame")
+# packets: the scan's packets in ONE contiguous uint8 array, ``packet_size`` apart; ts0: the smallest timestamp [ns] of a valid column
+OusterBatch = namedtuple("OusterBatch", "packets num_packets ts0")
+
+
+def ouster_packet_size(profile_name, H, C):
+    """LEGACY ``C (20 + 12 H)``; RNG19_RFL8_SIG16_NIR16 ``64 + C (12 + 12 H)``; RNG15_RFL8_NIR8 ``64 + C (12 + 4 H)``"""
+    if profile_name == "LEGACY":
+        return C * (20 + 12 * H)
+    return 64 + C * (12 + (12 if profile_name == "RNG19_RFL8_SIG16_NIR16" else 4) * H)
+
+
+def parse_packet_msg(data, cdr=False):
+    """``uint8[] buf``: a uint32 length and the bytes (CDR: behind the encapsulation header).  A zero-copy uint8 view of the packet."""
+    r = _reader(data, "ouster_msgs/msg/PacketMsg" if cdr else "ouster_ros/PacketMsg", cdr)
+    n = r.u32()
+    return np.frombuffer(r.take(n), dtype=np.uint8)
+
+
+def ouster_info(text, frame="sensor", where="the Ouster metadata"):
+    """The sensor's metadata JSON, flat (firmware 2) or in the groups of firmware 3, as the decode's tables.  ``frame``: ``sensor`` applies
+    ``lidar_to_sensor_transform``, ``lidar`` the identity.  Everything out of scope is refused by name, before any device is touched."""
+    if frame not in OUSTER_FRAMES:
+        raise ValueError(f"error: --ouster_frame {frame}: sensor and lidar are the options")
+    try:
+        doc = json.loads(text)
+    except ValueError as e:
+        raise ValueError(f"error: {where} is not JSON ({e})") from None
+    if not isinstance(doc, dict):
+        raise ValueError(f"error: {where} is not a JSON object")
+
+    def get(key, default=None):
+        for holder in [doc] + [doc[g] for g in OUSTER_GROUPS if isinstance(doc.get(g), dict)]:
+            if key in holder:
+                return holder[key]
+        return default
+
+    def numbers(key, value):
+        if not isinstance(value, list) or any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in value):
+            raise ValueError(f"error: {where}: {key} is not a list of numbers")
+        if not all(math.isfinite(v) for v in value):
+            raise ValueError(f"error: {where}: {key} holds a value that is not finite")
+        return [float(v) for v in value]
+
+    def integer(key, default=None):
+        v = get(key, default)
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"error: {where}: {key} is {'missing' if v is None else 'not an integer'}")
+        return v
+
+    name = get("udp_profile_lidar", "LEGACY")
+    if name not in OUSTER_PROFILES:
+        if isinstance(name, str) and "FUSA" in name:
+            raise ValueError(f"error: {where}: udp_profile_lidar {name}: the FUSA profiles are not decoded here ({', '.join(OUSTER_PROFILES)} are)")
+        if isinstance(name, str) and "DUAL" in name:
+            raise ValueError(f"error: {where}: udp_profile_lidar {name}: dual-return profiles are not decoded here ({', '.join(OUSTER_PROFILES)} are)")
+        raise ValueError(f"error: {where}: unknown udp_profile_lidar {name!r} ({', '.join(OUSTER_PROFILES)} are decoded here)")
+    altitude, azimuth = get("beam_altitude_angles"), get("beam_azimuth_angles")
+    if altitude is None or azimuth is None:
+        raise ValueError(f"error: {where}: no beam_altitude_angles / beam_azimuth_angles: not the metadata of an Ouster sensor")
+    altitude, azimuth = numbers("beam_altitude_angles", altitude), numbers("beam_azimuth_angles", azimuth)
+    H = integer("pixels_per_column", len(altitude))
+    if H not in (16, 32, 64, 128):
+        raise ValueError(f"error: {where}: pixels_per_column {H}: sensors of 16, 32, 64 and 128 beams are decoded here")
+    W = integer("columns_per_frame")
+    if not 16 <= W <= 4096:
+        raise ValueError(f"error: {where}: columns_per_frame {W} outside [16, 4096]")
+    C = integer("columns_per_packet", 16)
+    if not 1 <= C <= 16:
+        raise ValueError(f"error: {where}: columns_per_packet {C} outside [1, 16]")
+    if len(altitude) != H or len(azimuth) != H:
+        raise ValueError(f"error: {where}: {len(altitude)} beam_altitude_angles and {len(azimuth)} beam_azimuth_angles for pixels_per_column {H}")
+    n_mm = get("lidar_origin_to_beam_origin_mm", 0.0)
+    if isinstance(n_mm, bool) or not isinstance(n_mm, (int, float)) or not math.isfinite(n_mm):
+        raise ValueError(f"error: {where}: lidar_origin_to_beam_origin_mm is not a finite number")
+    if frame == "sensor":
+        transform = get("lidar_to_sensor_transform")
+        if transform is None:
+            raise ValueError(f"error: {where}: no lidar_to_sensor_transform, which --ouster_frame sensor applies (--ouster_frame lidar does without)")
+        transform = numbers("lidar_to_sensor_transform", transform)
+        if len(transform) != 16:
+            raise ValueError(f"error: {where}: lidar_to_sensor_transform has {len(transform)} entries, not 16")
+    else:
+        transform = [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0]
+    column_table = np.array([(math.cos(2.0 * math.pi * (1.0 - m / W)), math.sin(2.0 * math.pi * (1.0 - m / W))) for m in range(W)], dtype=np.float64)
+    beam_table = np.array([(math.cos(-math.radians(azimuth[i])), math.sin(-math.radians(azimuth[i])), math.cos(math.radians(altitude[i])), math.sin(math.radians(altitude[i])))
+                           for i in range(H)], dtype=np.float64)
+    return OusterInfo(name, OUSTER_PROFILES[name], H, W, C, ouster_packet_size(name, H, C), column_table, beam_table, float(n_mm), np.array(transform[:12], dtype=np.float64), frame)
+
+
+def ouster_columns(packets, info):
+    """Of a (n, packet_size) uint8 array: ``(timestamp uint64, measurement_id, valid)`` per column, each (n, C), and the ``frame_id`` (n,)"""
+    n = packets.shape[0]
+    legacy = info.profile_name == "LEGACY"
+    column_bytes = (info.packet_size - (0 if legacy else 64)) // info.C
+    cols = packets[:, (0 if legacy else 32) : (0 if legacy else 32) + info.C * column_bytes].reshape(n, info.C, column_bytes)
+    timestamp = np.ascontiguousarray(cols[:, :, 0:8]).view("<u8").reshape(n, info.C)
+    measurement_id = np.ascontiguousarray(cols[:, :, 8:10]).view("<u2").reshape(n, info.C)
+    if legacy:
+        valid = np.ascontiguousarray(cols[:, :, column_bytes - 4 :]).view("<u4").reshape(n, info.C) == 0xFFFFFFFF
+        frame_id = np.ascontiguousarray(packets[:, 10:12]).view("<u2").reshape(n)
+    else:
+        valid = (np.ascontiguousarray(cols[:, :, 10:12]).view("<u2").reshape(n, info.C) & 1) != 0
+        frame_id = np.ascontiguousarray(packets[:, 2:4]).view("<u2").reshape(n)
+    return timestamp, measurement_id, valid, frame_id
+
+
+def batch_points(messages, cdr=False, lidar=None, warn=None, where=""):
+    """The messages of a points topic with the PacketMsg ones grouped into scans: every other message passes through untouched and in
+    order; a run of PacketMsg messages becomes one message per scan -- same connection, topic and type, the record time of the scan's
+    first packet -- whose ``data`` is an ``OusterBatch``.  A scan closes when the packets' ``frame_id`` changes (LEGACY: uint16 at byte
+    10 of the first column header; else uint16 at byte 2 of the packet header), when the topic ends or a message of another kind
+    comes, or when it holds ``2 ceil(W / C)`` packets (one warning per bag).  Partial first and last scans are kept; a scan without a valid
+    column is skipped with a warning.  A buffer that is not ``packet_size`` long is refused."""
+    warn = warn or (lambda msg: None)
+    info = getattr(lidar, "ouster", None)
+    pending, frame_id, capped = [], None, [False]
+
+    def close():
+        first = pending[0][0]
+        packets = np.empty((len(pending), info.packet_size), dtype=np.uint8)  # the one copy: contiguous, stride = packet size
+        for k, (_, buf) in enumerate(pending):
+            packets[k] = buf
+        pending.clear()
+        timestamp, _, valid, _ = ouster_columns(packets, info)
+        if not valid.any():
+            warn(f"warning: skip a scan of {packets.shape[0]} Ouster packet(s) without a valid column {where}")
+            return None
+        return first._replace(data=OusterBatch(packets.reshape(-1), packets.shape[0], int(timestamp[valid].min())))
+
+    for k, m in enumerate(messages):
+        if points_kind(m.type) != "PacketMsg":
+            if pending:
+                out = close()
+                if out is not None:
+                    yield out
+            yield m
+            continue
+        if info is None:
+            raise ValueError(f"error: Ouster packets on topic '{m.topic}' {where} need the sensor's metadata: --ouster_metadata auto (a std_msgs/String topic whose name ends in "
+                             "'metadata') or --ouster_metadata FILE.json")
+        buf = parse_packet_msg(m.data, cdr)
+        if buf.size != info.packet_size:
+            raise ValueError(f"error: message {k} of topic '{m.topic}' {where} holds a buffer of {buf.size} bytes, where a {info.profile_name} lidar packet of "
+                             f"{info.H} x {info.C} pixels has {info.packet_size}: not a lidar packet of this sensor (the IMU packets are 48 bytes)")
+        fid = int(buf[10]) | int(buf[11]) << 8 if info.profile_name == "LEGACY" else int(buf[2]) | int(buf[3]) << 8
+        if pending and fid != frame_id:
+            out = close()
+            if out is not None:
+                yield out
+        frame_id = fid
+        pending.append((m, buf))
+        if len(pending) == 2 * -(-info.W // info.C):
+            if not capped[0]:
+                warn(f"warning: {len(pending)} Ouster packets with frame_id {fid}, two turns of {info.W} columns, {where}: the scan is closed there")
+                capped[0] = True
+            out = close()
+            if out is not None:
+                yield out
+    if pending:
+        out = close()
+        if out is not None:
+            yield out
+
+
+def ouster_decode(packets, num_packets, stride, info, ts0, device=0, returns=False):
+    """``nidreg_ouster_decode``: ``packets`` a uint8 array whose packet p lies at byte ``p * stride`` (any address).  Returns the
+    (num_packets * C * H, 8) uint32 records (32 bytes each: x y z intensity t reflectivity|ring ambient range), with ``returns=True`` also
+    the per-packet counts of decoded returns.  A refusal of the entry point is a ``ValueError``."""
+    from . import _lib
+
+    n = int(num_packets)
+    packets = np.asarray(packets)
+    if packets.dtype != np.uint8 or packets.ndim != 1 or (packets.size > 1 and packets.strides[0] != 1):
+        raise ValueError("ouster_decode: packets must be a contiguous uint8 array")
+    ok = 0 <= n <= OUSTER_MAX_PACKETS and info.H in (16, 32, 64, 128) and 1 <= info.C <= 16
+    if ok and n > 0 and stride >= info.packet_size and packets.size < (n - 1) * stride + info.packet_size:
+        raise ValueError(f"ouster_decode: {packets.size} bytes for {n} packets of stride {stride}")
+    column_table = np.ascontiguousarray(info.column_table, dtype=np.float64)
+    beam_table = np.ascontiguousarray(info.beam_table, dtype=np.float64)
+    transform12 = np.ascontiguousarray(info.transform12, dtype=np.float64)
+    if ok and (column_table.shape != (info.W, 2) or beam_table.shape != (info.H, 4) or transform12.shape != (12,)):
+        raise ValueError(f"ouster_decode: tables of shapes {column_table.shape}, {beam_table.shape}, {transform12.shape} for W = {info.W}, H = {info.H}")
+    records = np.empty((n * info.C * info.H if ok else 0, 8), dtype=np.uint32)  # (a call the entry point will refuse gets no buffer)
+    counts = np.zeros(n if ok else 0, dtype=np.int32) if returns else None
+    lib = _lib.load()
+    rc = lib.nidreg_ouster_decode(int(device), packets.ctypes.data if packets.size else None, n, int(stride), int(info.profile), int(info.H), int(info.W), int(info.C),
+                                  column_table.ctypes.data_as(_lib.c_double_p), beam_table.ctypes.data_as(_lib.c_double_p), float(info.n_mm), transform12.ctypes.data_as(_lib.c_double_p),
+                                  int(ts0), records.ctypes.data if records.size else None, None if counts is None else counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    if rc == _lib.NIDREG_ERR_INVALID:
+        raise ValueError(_lib.last_error())
+    _lib.check(rc, "nidreg_ouster_decode")
+    return (records, counts) if returns else records
+
+
+def ouster_cloud(batch, info, device=0, header_only=False, frame_id="os_sensor"):
+    """The cloud of one scan: 32-byte records, one per pixel of every received column in the order packet, column, pixel, height 1, the
+    stamp ``ts0`` -- the smallest timestamp of a valid column -- as (sec, nsec).  ``header_only``: the fields without the records."""
+    if header_only or batch is None or batch.num_packets == 0:
+        return PointCloud2((0, 0), frame_id, 1, 0, list(OUSTER_FIELDS), 0, OUSTER_RECORD_BYTES, 0, np.zeros(0, dtype=np.uint8), 0)
+    if batch.num_packets > OUSTER_MAX_PACKETS:
+        raise ValueError(f"error: a scan of {batch.num_packets} Ouster packets: at most {OUSTER_MAX_PACKETS} are decoded in one call")
+    records = ouster_decode(batch.packets, batch.num_packets, info.packet_size, info, batch.ts0, device=device)
+    width = records.shape[0]
+    stamp = (batch.ts0 // 1000000000, batch.ts0 % 1000000000)
+    return PointCloud2(stamp, "os_lidar" if info.frame == "lidar" else frame_id, 1, width, list(OUSTER_FIELDS), 0, OUSTER_RECORD_BYTES, OUSTER_RECORD_BYTES * width,
+                       records.reshape(-1).view(np.uint8), 0)
 
 
 # ---------------------------------------------------------------------------------------------- the GPU decode
@@ -266,4 +501,17 @@ def decode_points(type_name, data, cdr=False, lidar=None, device=0, where="", he
         return velodyne_cloud(parse_velodyne_scan(data, cdr), lidar, device=device, where=where, header_only=header_only)
     if kind == "CustomMsg":
         return parse_livox_custom(data, cdr)
+    if kind == "PacketMsg":
+        if header_only:
+            return ouster_cloud(None, None, header_only=True)
+        info = getattr(lidar, "ouster", None)
+        if info is None:
+            raise ValueError(f"error: Ouster packets {where} need the sensor's metadata: --ouster_metadata auto (a std_msgs/String topic whose name ends in 'metadata') or "
+                             "--ouster_metadata FILE.json")
+        if not isinstance(data, OusterBatch):  # one message on its own: a scan of one packet
+            data = next(iter(batch_points([rosbag1.Message(0, "", type_name, (0, 0), data)], cdr=cdr, lidar=lidar, where=where)), None)
+            if data is None:
+                return ouster_cloud(None, None, header_only=True)
+            data = data.data
+        return ouster_cloud(data, info, device=device)
     return None

@@ -18,6 +18,9 @@ GPU (``StaticPointCloudIntegrator.insert_cloud2``).  Differences from the refere
 * a points topic of ``velodyne_msgs/VelodyneScan`` (the raw packets of a VLP-16 / HDL-32E, decoded on the GPU: ``--lidar_model``,
   ``--velodyne_calibration``) or ``livox_ros_driver(2)/CustomMsg`` is read in a PointCloud2 topic's place (``lidar_messages``, unpinned
   against the vendor drivers); with ``-a`` only in a bag that has no PointCloud2 topic.  The reference needs the driver's cloud;
+* a points topic of ``ouster_ros/PacketMsg`` (one UDP packet of an Ouster sensor a message; with ``-a`` a topic whose name ends in
+  ``lidar_packets``) is batched into scans and decoded on the GPU likewise: ``--ouster_metadata auto|FILE.json`` gives the sensor's
+  geometry, ``--ouster_frame sensor|lidar`` the frame of the points.  The records come in packet order, not the driver's H x W image;
 
 * ``-d / --dynamic_lidar_integration`` is refused here with status 1 and a message: the dynamic LiDAR integration (CT-GICP) is a
   command of its own, ``preprocess_dynamic``, which runs this module's ``run`` with ``odometry.DynamicPointCloudIntegrator``;
@@ -66,10 +69,16 @@ def build_parser():
     p.add_argument("--camera_info_topic")
     p.add_argument("--image_topic", help="sensor_msgs/Image, or CompressedImage with a PNG or baseline JPEG payload; a JPEG is decoded as cv_bridge::toCvCopy(msg, mono8) decodes "
                                          "it (to BGR, then luma), which is not the Y plane cv::imread(path, 0) returns")
-    p.add_argument("--points_topic", help="sensor_msgs/PointCloud2, velodyne_msgs/VelodyneScan (the raw packets, decoded on the GPU) or livox_ros_driver(2)/CustomMsg")
+    p.add_argument("--points_topic", help="sensor_msgs/PointCloud2, velodyne_msgs/VelodyneScan (the raw packets, decoded on the GPU), livox_ros_driver(2)/CustomMsg or ouster_ros/PacketMsg "
+                                          "(the lidar packets, decoded on the GPU: --ouster_metadata)")
     p.add_argument("--lidar_model", default="auto", choices=("auto",) + lidar_messages.LIDAR_MODELS,
                    help="packet layout and laser angles of a VelodyneScan topic: auto reads the product id of the first packet (extension)")
     p.add_argument("--velodyne_calibration", help="the vendor driver's calibration YAML (16 or 32 lasers) in place of the built-in angles of a VelodyneScan topic (extension)")
+    p.add_argument("--ouster_metadata", default="auto", help="the sensor's metadata JSON for a points topic of Ouster packets (ouster_ros/PacketMsg): auto takes the first message of a "
+                                                              "std_msgs/String topic of the bag whose name ends in 'metadata', else a FILE.json (extension)")
+    p.add_argument("--ouster_frame", default="sensor", choices=lidar_messages.OUSTER_FRAMES,
+                   help="frame of the points decoded from Ouster packets, and so the frame T_lidar_camera is expressed in: sensor applies the metadata's lidar_to_sensor_transform, "
+                        "lidar the identity (extension)")
     p.add_argument("--camera_model", default="auto", help="auto, atan, plumb_bob, fisheye(=equidistant), omnidir, or equirectangular")
     p.add_argument("--camera_intrinsics", help="camera intrinsic parameters [fx,fy,cx,cy(,xi)] (don't put spaces between values!!)")
     p.add_argument("--camera_distortion_coeffs", help="camera distortion parameters [k1,k2,p1,p2,k3] (don't put spaces between values!!)")
@@ -108,7 +117,8 @@ def get_topics(args, bag, log=print, warn=_warn):
                 if points_topic:
                     warn("warning: bag constains multiple points topics!!")
                 points_topic = topic
-            elif "VelodyneScan" in type_ or "CustomMsg" in type_:  # read in a PointCloud2 topic's place, never beside one
+            # read in a PointCloud2 topic's place, never beside one; the Ouster IMU packets have the lidar packets' type, so the name decides
+            elif "VelodyneScan" in type_ or "CustomMsg" in type_ or (lidar_messages.points_kind(type_) == "PacketMsg" and topic.endswith("lidar_packets")):
                 if packets_topic:
                     warn("warning: bag constains multiple points topics!!")
                 packets_topic = topic
@@ -226,7 +236,9 @@ def integrate_bag(args, bag, points_topic, intensity_channel, integrator, warn=_
     keeper = preprocess.TimeKeeper(log=warn)
     timed = getattr(integrator, "insert_cloud2_timed", None)
     inserted = rewound = nonfinite = 0
-    for k, m in enumerate(bag.messages(points_topic)):
+    # (Ouster packets arrive here as one message per scan: ``batch_points`` groups them; every other message passes through it untouched)
+    scans = reader.batch_points(bag.messages(points_topic), lidar=lidar, warn=warn, where=f"(points topic '{points_topic}' in {bag.path})")
+    for k, m in enumerate(scans):
         where = f"(message {k} of points topic '{points_topic}' in {bag.path})"
         if lidar_messages.points_kind(m.type) is None:
             break  # read_next returns nullptr at the first message that does not instantiate (src/preprocess_ros1.cpp:33-36)
@@ -261,14 +273,38 @@ def integrate_bag(args, bag, points_topic, intensity_channel, integrator, warn=_
     return inserted, rewound, nonfinite
 
 
-def lidar_options(args, bag, points_topic, log=print):
+def ouster_metadata(args, bag, points_topic, reader=rosbag1):
+    """``--ouster_metadata`` and ``--ouster_frame`` as ``lidar_messages.OusterInfo``: the JSON of the named file, or with ``auto`` the first
+    message of a ``std_msgs/String`` topic of the bag whose name ends in ``metadata``"""
+    source, frame = getattr(args, "ouster_metadata", "auto") or "auto", getattr(args, "ouster_frame", "sensor")
+    if source != "auto":
+        with open(source) as f:
+            return lidar_messages.ouster_info(f.read(), frame, where=source)
+    for topic, type_ in bag.topics_and_types():
+        if topic.endswith("metadata") and (type_.endswith("/String") or type_ == "String"):
+            m = bag.first_message(topic, "String")
+            if m is not None:
+                where = f"the first message of topic '{topic}' in {bag.path}"
+                return lidar_messages.ouster_info(reader.decode_string(m.data), frame, where=where)
+    raise ValueError(f"error: points topic '{points_topic}' in {bag.path} holds Ouster packets, and the bag has no std_msgs/String topic whose name ends in 'metadata': "
+                     "name the sensor's metadata JSON with --ouster_metadata FILE.json")
+
+
+def lidar_options(args, bag, points_topic, log=print, reader=rosbag1):
     """``--lidar_model`` and ``--velodyne_calibration`` as ``lidar_messages.LidarOptions`` when the points topic is a VelodyneScan one;
-    for any other topic they are ignored, with one logged line if either was given, and the result is ``None``"""
+    for any other topic they are ignored, with one logged line if either was given, and the result is ``None``.  ``--ouster_metadata``
+    and ``--ouster_frame`` likewise: options with the sensor's ``OusterInfo`` when the points topic is a PacketMsg one, else one logged
+    line if either was given."""
     lidar_model, calibration = getattr(args, "lidar_model", "auto"), getattr(args, "velodyne_calibration", None)
-    if any(topic == points_topic and lidar_messages.points_kind(type_) == "VelodyneScan" for topic, type_ in bag.topics_and_types()):
+    kinds = [lidar_messages.points_kind(type_) for topic, type_ in bag.topics_and_types() if topic == points_topic]
+    if "PacketMsg" not in kinds and (getattr(args, "ouster_metadata", "auto") not in (None, "auto") or getattr(args, "ouster_frame", "sensor") != "sensor"):
+        log(f"--ouster_metadata and --ouster_frame are ignored: points topic '{points_topic}' is not an ouster_ros/PacketMsg topic")
+    if "VelodyneScan" in kinds:
         return lidar_messages.LidarOptions(lidar_model, calibration)
     if lidar_model != "auto" or calibration:
         log(f"--lidar_model and --velodyne_calibration are ignored: points topic '{points_topic}' is not a velodyne_msgs/VelodyneScan topic")
+    if "PacketMsg" in kinds:
+        return lidar_messages.LidarOptions(ouster=ouster_metadata(args, bag, points_topic, reader=reader))
     return None
 
 
@@ -302,7 +338,7 @@ def run(args, log=print, warn=_warn, integrator_factory=preprocess.StaticPointCl
     log(f"- camera_info: {camera_info_topic}")
     log(f"- image      : {image_topic}")
     log(f"- points     : {points_topic}")
-    lidar = lidar_options(args, first, points_topic, log=log)
+    lidar = lidar_options(args, first, points_topic, log=log, reader=reader)
     intensity_channel = get_intensity_channel(args, first, points_topic, reader=reader)
     log(f"intensity_channel: {intensity_channel}")
     camera_model, image_size, intrinsics, distortion = get_camera_params(args, first, camera_info_topic, image_topic, log=log, reader=reader)

@@ -254,6 +254,19 @@ def decode_points(type_name, data, **kw):
     return lidar_messages.decode_points(type_name, data, cdr=False, **kw)
 
 
+def batch_points(messages, **kw):
+    """The messages of a points topic with its ``ouster_ros/PacketMsg`` messages -- one UDP packet each -- grouped into one message per
+    scan, which ``decode_points`` takes; every other message passes through untouched (``lidar_messages.batch_points``)"""
+    from . import lidar_messages
+
+    return lidar_messages.batch_points(messages, cdr=False, **kw)
+
+
+def decode_string(data):
+    """std_msgs/String"""
+    return _Reader(data, "std_msgs/String").string()
+
+
 def decode_image(data):
     """sensor_msgs/Image; ``data`` is a zero-copy uint8 view"""
     r = _Reader(data, "sensor_msgs/Image")

@@ -470,6 +470,18 @@ def decode_points(type_name, data, **kw):
     return lidar_messages.decode_points(type_name, data, cdr=True, **kw)
 
 
+def batch_points(messages, **kw):
+    """``rosbag1.batch_points`` for CDR blobs (``ouster_msgs/msg/PacketMsg``, ``ouster_sensor_msgs/msg/PacketMsg``)"""
+    from . import lidar_messages
+
+    return lidar_messages.batch_points(messages, cdr=True, **kw)
+
+
+def decode_string(data):
+    """std_msgs/msg/String"""
+    return _Cdr(data, "std_msgs/msg/String").string()
+
+
 def decode_image(data):
     """sensor_msgs/msg/Image; ``data`` is a zero-copy uint8 view"""
     r = _Cdr(data, "sensor_msgs/msg/Image")

@@ -707,6 +707,51 @@ int nidreg_velodyne_decode(int device_id, const uint8_t* packets, int64_t num_pa
                            double distance_resolution, double firing_period, double laser_period, float* records_out, int32_t* returns_per_packet);
 int nidreg_velodyne_get_timing(double* ms3);
 
+/* ---- Ouster lidar packets to point records (csrc/nid_ouster_kernels.hpp; Python: lidar_messages.py) ------------------------------
+ * What ouster_ros does between a bag of ouster_ros/PacketMsg -- one UDP packet a message, batched into scans by the caller -- and
+ * extract_raw_points: the packets of one scan become 32-byte point records.  Stateless (nothing stays on a device); all pointers
+ * are host memory; one workgroup per column, no atomics: the same bytes on every run, restated byte for byte in
+ * tests/ouster_oracle.py.  The layouts and the geometry restate the sensor's software manual and the SDK's field tables from
+ * memory: the result is UNPINNED against ouster_ros, the Ouster SDK and real recordings.
+ * SOURCE  packets: num_packets packets, packet_stride bytes apart, at any address; little-endian.  H pixels per column, C columns
+ * per packet, W columns per frame.
+ *   NIDREG_OUSTER_LEGACY  no packet header.  A column is 16 + 12 H + 4 bytes: uint64 timestamp [ns] @0, uint16 measurement_id @8,
+ *       uint16 frame_id @10, uint32 encoder @12 (unused); H pixels of 12 bytes -- range = uint32 @0 & 0x000FFFFF [mm], reflectivity
+ *       uint16 @4, signal uint16 @6, near_ir uint16 @8 --; a uint32 status, the column being valid iff it is 0xFFFFFFFF.
+ *       Packet: C (20 + 12 H) bytes.
+ *   NIDREG_OUSTER_RNG19_RFL8_SIG16_NIR16  32-byte packet header (frame_id: uint16 @2), 32-byte footer, both ignored here.  A column
+ *       is 12 + 12 H bytes: uint64 timestamp @0, uint16 measurement_id @8, uint16 status @10, valid iff bit 0 is set; pixels of 12
+ *       bytes -- range = uint32 @0 & 0x0007FFFF, reflectivity uint8 @4, signal uint16 @6, near_ir uint16 @8.  Packet: 64 + C (12 + 12 H).
+ *   NIDREG_OUSTER_RNG15_RFL8_NIR8  the same headers; pixels of 4 bytes -- range = (uint16 @0 & 0x7FFF) << 3, reflectivity uint8 @2,
+ *       near_ir = uint8 @3 << 4, signal = 0.  Packet: 64 + C (12 + 4 H).
+ * TABLES  the caller's, built with libm: column_table[m] = (cos E, sin E), E = 2 pi (1 - m / W), m = 0..W-1; beam_table[i] =
+ * (cos A, sin A, cos P, sin P), A = -radians(beam_azimuth_angles[i]), P = radians(beam_altitude_angles[i]), i = 0..H-1; n_mm =
+ * lidar_origin_to_beam_origin_mm; transform12 = the first three rows of the row-major 4 x 4 lidar_to_sensor_transform (R00 R01 R02 t0,
+ * R10 ..., millimetres), or of the identity for records in the lidar frame.
+ * OUTPUT  record (packet * C + column) * H + pixel -- the byte order of the packets, NOT the driver's destaggered H x W image -- is
+ * 32 bytes: x, y, z float32 [m] @0 4 8, intensity float32 @12 (= signal), t uint32 [ns] @16, reflectivity uint16 @20, ring uint16 @22
+ * (= pixel), ambient uint16 @24 (= near_ir), zero @26..27, range uint32 [mm] @28.
+ *   t = min(timestamp - ts0, 2^32 - 1) in unsigned 64-bit arithmetic; the caller passes the smallest timestamp of the valid columns
+ *   a pixel is "no return" when its column is not valid, or measurement_id >= W (the column table is then not read), or range = 0:
+ *   x = y = z = quiet NaN (0x7FC00000), every other field zero but ring and t
+ *   else, in fp64 without contraction, m = measurement_id, (cosE, sinE) = column_table[m], (cosA, sinA, cosP, sinP) = beam_table[i]:
+ *       c = cosE cosA - sinE sinA;  s = sinE cosA + cosE sinA;  d = double(range) - n
+ *       lx = d (c cosP) + n cosE;  ly = d (s cosP) + n sinE;  lz = d sinP
+ *       X = ((R00 lx + R01 ly) + R02 lz) + t0, rows 1 and 2 alike;  x = float32(X 0.001)
+ *   returns_per_packet (nullable): per packet, the number of records that are not "no return".
+ * Refused with NIDREG_ERR_INVALID and a message, before the device is touched and with nothing written: a profile other than the
+ * three; H not 16, 32, 64 or 128; W outside [16, 4096]; C outside [1, 16]; packet_stride below the packet size or above 32768;
+ * num_packets outside [0, 4096]; a NULL packets, column_table, beam_table, transform12 or records_out with num_packets > 0; a table
+ * entry, transform entry or n_mm that is not finite.  num_packets == 0 succeeds without a device.
+ *   nidreg_ouster_get_timing  host wall-clock milliseconds of the calling thread's last nidreg_ouster_decode: [0] allocation and
+ *                             upload, [1] the kernels (launch to idle), [2] copy back. */
+#define NIDREG_OUSTER_LEGACY 0
+#define NIDREG_OUSTER_RNG19_RFL8_SIG16_NIR16 1
+#define NIDREG_OUSTER_RNG15_RFL8_NIR8 2
+int nidreg_ouster_decode(int device_id, const uint8_t* packets, int64_t num_packets, int64_t packet_stride, int profile, int H, int W, int C, const double* column_table,
+                         const double* beam_table, double n_mm, const double* transform12, uint64_t ts0, void* records_out, int32_t* returns_per_packet);
+int nidreg_ouster_get_timing(double* ms3);
+
 /* ---- match pictures: a 2-D primitive rasteriser (csrc/nid_draw_kernels.hpp; Python: draw.py) ------------------------------------
  * What find_matches --picture and initial_guess_auto --picture draw with, in place of the reference script's OpenCV calls
  * (scripts/find_matches_superglue.py: both images side by side, keypoints circled, matches as lines).  Stateless; all pointers are
