@@ -18,6 +18,7 @@ NIDREG_ERR_FULL = -4
 NIDREG_OUT_DOUBLES = 16
 FEATURES_CAPACITY = 65536  # NIDREG_FEATURES_CAPACITY
 SELECT_TILE = 1024  # NIDREG_SELECT_TILE
+FOLD_MAX = 1024  # NIDREG_FOLD_MAX
 
 MODE_SPLINE, MODE_NEAREST = 0, 1
 PREC_FP64 = 0  # (1 = NIDREG_PREC_FP32: removed in round 5, refused by nidreg_create)
@@ -87,6 +88,7 @@ EXPORTS = [
     "nidreg_ouster_decode", "nidreg_ouster_get_timing",
     "nidreg_draw",
     "nidreg_mask_create", "nidreg_mask_get", "nidreg_mask_destroy", "nidreg_cloud_select", "nidreg_cloud_select_counts", "nidreg_cloud_size", "nidreg_cloud_get",
+    "nidreg_cloud_fold_ids", "nidreg_cloud_fold",
 ]
 
 _lib = None
@@ -215,6 +217,8 @@ def load():
     lib.nidreg_cloud_size.argtypes = [ctypes.c_void_p, c_int64_p]
     lib.nidreg_cloud_get.argtypes = [ctypes.c_void_p, c_double_p, c_double_p]
     lib.nidreg_cloud_select_counts.argtypes = [ctypes.c_void_p, c_int64_p]
+    lib.nidreg_cloud_fold_ids.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_double, ctypes.c_int, c_int32_p, c_int64_p]
+    lib.nidreg_cloud_fold.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), c_int32_p, c_int64_p]
     # test hook (csrc/nidreg_abi.hip, not declared in include/nidreg.h): a plain handle's records as the builder left them
     lib.nidreg_debug_records.argtypes = [ctypes.c_void_p, c_int64_p, c_int64_p, ctypes.c_int64, c_double_p, c_int32_p, ctypes.c_int64]
     lib.nidreg_rccl_unique_id.argtypes = [ctypes.c_char_p]
@@ -231,7 +235,7 @@ def kernel_source_hash():
     import hashlib
 
     h = hashlib.sha256()
-    names = ["nid_device.hpp", "nid_atan_table.hpp", "nid_log_table.hpp", "nid_multi.hpp", "nid_kernels.hpp", "nid_fused.hpp", "nid_launch_impl.hpp", "nid_kernels_f64.hip", "nid_kernels_f64_exact.hip", "nid_kernels_fused.hip", "nid_select_kernels.hpp", "nidreg_select.hip", "Makefile"]
+    names = ["nid_device.hpp", "nid_atan_table.hpp", "nid_log_table.hpp", "nid_multi.hpp", "nid_kernels.hpp", "nid_fused.hpp", "nid_launch_impl.hpp", "nid_kernels_f64.hip", "nid_kernels_f64_exact.hip", "nid_kernels_fused.hip", "nid_select_kernels.hpp", "nidreg_select.hip", "nid_fold_kernels.hpp", "nidreg_fold.hip", "Makefile"]
     for path in [os.path.join(CSRC_DIR, n) for n in names]:
         h.update(os.path.basename(path).encode())
         with open(path, "rb") as f:

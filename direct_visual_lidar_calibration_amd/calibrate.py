@@ -66,7 +66,7 @@ def _upload(points, intensities, device):
     return nid.Cloud(points, intensities, device=device)
 
 
-def calibrate_pairs(proj, pairs, init_x, params, precision="fp64", stats=None, selection=None, log=None):
+def calibrate_pairs(proj, pairs, init_x, params, precision="fp64", stats=None, selection=None, log=None, clouds=None, after=None):
     """The in-memory body of the command: ``pairs`` = [(image_u8 (H, W), points (N, 4), intensities (N,)), ...] as
     ``VisualLiDARData`` holds them -- or (image_u8, xyz float32 (N, 3), intensities float32 (N,)) as the file stores them, uploaded
     without a host widening pass -- ``init_x`` the Sophus-order ``T_camera_lidar`` 7-vector.  One upload per pair; every outer
@@ -76,14 +76,22 @@ def calibrate_pairs(proj, pairs, init_x, params, precision="fp64", stats=None, s
     ``selection`` (optional): ``{"masks": [mask_u8 (H, W) | None per pair], "margin", "min_range", "max_range"}`` -- every outer
     iteration then takes its points from ``Cloud.select`` (cull, eroded mask, range gate) and builds the cost object from the selected
     cloud with ``cull=None``; ``log`` receives one line per pair and outer iteration with what the cull kept and what the mask and the
-    range removed."""
+    range removed.
+    ``clouds`` (optional): one ``nid.Cloud`` per pair, already on its device and owned by the caller -- nothing is uploaded
+    (``upload_s`` is 0) and nothing is closed; the pairs' points and intensities may then be ``None``.
+    ``after`` (optional): called as ``after(x, cal)`` once the calibration has ended, while the clouds and the masks still exist:
+    ``cal.fused_nid_factory(k, T, bins)`` then builds pair ``k``'s cost object as the outer iterations did."""
     ndev = _lib.load().nidreg_device_count()
     if ndev <= 0:
         raise SystemExit("error: no MI355X / HIP device visible (the NID core has no CPU fallback)")
+    owned = clouds is None
+    if not owned and len(clouds) != len(pairs):
+        raise ValueError(f"{len(clouds)} clouds for {len(pairs)} pairs")
     t0 = time.perf_counter()
-    clouds = [_upload(p[1], p[2], k % ndev) for k, p in enumerate(pairs)]
+    if owned:
+        clouds = [_upload(p[1], p[2], k % ndev) for k, p in enumerate(pairs)]
+    upload_s = time.perf_counter() - t0 if owned else 0.0
     images_f64 = [p[0].astype(np.float64) * (1.0 / 255.0) for p in pairs]  # convertTo(CV_64FC1, 1/255), :204
-    upload_s = time.perf_counter() - t0
     size = (pairs[0][0].shape[1], pairs[0][0].shape[0])
     max_fov = nid.estimate_camera_fov(proj, size)
     min_z = math.cos(max_fov)
@@ -106,7 +114,7 @@ def calibrate_pairs(proj, pairs, init_x, params, precision="fp64", stats=None, s
     if selection is not None:
         # the select route: sub = clouds[k].select(...) -> from_cloud(..., sub, cull=None) -> sub.close().  scale_points keeps the
         # fixed-point unit of the whole cloud, as the fused route has it.
-        masks = [None if m is None else nid.Mask(m, margin=selection["margin"], device=k % ndev) for k, m in enumerate(selection["masks"])]
+        masks = [None if m is None else nid.Mask(m, margin=selection["margin"], device=clouds[k].device) for k, m in enumerate(selection["masks"])]
 
         def selected(k, T):
             sub = clouds[k].select(proj, size, T, min_z, depth, mask=masks[k], min_range=selection["min_range"], max_range=selection["max_range"])
@@ -136,8 +144,11 @@ def calibrate_pairs(proj, pairs, init_x, params, precision="fp64", stats=None, s
         [(p[0], None, None) for p in pairs], params, fused_nid_factory=fused_nid if selection is None else selected_nid,
         fused_nearest_factory=fused_nearest if selection is None else selected_nearest, multi_factory=lambda init, costs: _Multi(init, costs))
     x = cal.calibrate(init_x)
-    for c in clouds:
-        c.close()
+    if after is not None:
+        after(x, cal)
+    if owned:
+        for c in clouds:
+            c.close()
     for m in masks:
         if m is not None:
             m.close()
@@ -147,7 +158,9 @@ def calibrate_pairs(proj, pairs, init_x, params, precision="fp64", stats=None, s
     return x, cal
 
 
-def run(args, log=print):
+def prepare(args, log=print):
+    """What ``run`` does before a device is touched (``evaluate`` starts the same way, with the same error lines): the directory, the
+    camera, the initial guess, the parameters and the selection.  Returns ``(config, bags, proj, init_x, params, sel)``."""
     config, bags = dataset.load_dataset(args.data_path, args.first_n_bags)
     if args.first_n_bags is not None:
         log(f"use only the first {args.first_n_bags} bags")
@@ -174,6 +187,11 @@ def run(args, log=print):
         # (every mask is read and checked against its image here, on the host, before a cloud goes up)
         sel["masks"] = [dataset.load_mask(args.data_path, b.bag_name, sel["mask"], b.image.shape, log=log) for b in bags]
         log(f"selection: mask {sel['mask']}, margin {sel['margin']} px, range [{sel['min_range']}, {sel['max_range']}] m")
+    return config, bags, proj, init_x, params, sel
+
+
+def run(args, log=print):
+    config, bags, proj, init_x, params, sel = prepare(args, log)
     if args.dry_run:
         return config, init_x, None
 

@@ -89,6 +89,13 @@ void estimate_direction_host(int model, const double* intr5, const double* dist8
 hipError_t launch_cull(int model, const double* intr, const double* dist, const double* d_pts, long long stride_d, long long n, const double* T, int W, int H, double min_z,
                        int depth, int* d_pix, unsigned int* d_zbuf, unsigned char* d_keep, hipStream_t stream);
 
+// the compaction of nidreg_cloud_select behind another flag pass (nidreg_select.hip: k_select_scan, k_select_scatter as they are; null
+// stream; all pointers are device memory).  d_count: 3 x ntiles words, the first ntiles the tiles' flagged points; d_offset: ntiles + 3
+// words, [ntiles] the total; d_idx_out nullable
+hipError_t launch_select_scan(const int* d_count, int ntiles, int* d_offset);
+hipError_t launch_select_scatter(const unsigned char* d_flag, const int* d_offset, int ntiles, const double* d_pts, const double* d_int, long long n, int32_t* d_idx_out, double* d_pts_out,
+                                 double* d_int_out);
+
 // PointsColorUpdater::update / generate_lidar_image (nid_render_kernels.hpp); all pointers are device memory,
 // T = rows of the 4x4 T_camera_lidar
 hipError_t launch_colorize(int model, const double* intr, const double* dist, const double* d_pts, long long stride_d, long long n, const double* T, const uint8_t* d_img, int W, int H,

@@ -19,6 +19,22 @@ bool size_ok(int width, int height) { return width >= 1 && width <= kMaskMaxDim 
 
 }  // namespace
 
+// the compaction behind another flag pass (nidreg_fold.hip; declared in nid_launch.hpp): the two kernels as nidreg_cloud_select launches them
+namespace nidreg {
+
+hipError_t launch_select_scan(const int* d_count, int ntiles, int* d_offset) {
+  hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(kSelectThreads), 0, nullptr, d_count, ntiles, d_offset);
+  return hipGetLastError();
+}
+
+hipError_t launch_select_scatter(const unsigned char* d_flag, const int* d_offset, int ntiles, const double* d_pts, const double* d_int, long long n, int32_t* d_idx_out, double* d_pts_out,
+                                 double* d_int_out) {
+  hipLaunchKernelGGL(k_select_scatter, dim3(unsigned(ntiles)), dim3(kSelectThreads), 0, nullptr, d_flag, d_offset, d_pts, d_int, n, d_idx_out, d_pts_out, d_int_out);
+  return hipGetLastError();
+}
+
+}  // namespace nidreg
+
 extern "C" {
 
 int nidreg_mask_create(int device_id, const uint8_t* mask, int width, int height, int64_t row_stride, int margin, nidreg_mask** out) {

@@ -172,6 +172,33 @@ class Cloud:
         sub.select_counts = {"culled_kept": int(c3[0]), "mask_removed": int(c3[1]), "range_removed": int(c3[2])}  # (of this cloud's points; for the log)
         return (sub, idx[: sub.num_points].copy()) if return_indices else sub
 
+    def fold_ids(self, seed, num_folds, cell=0.0):
+        """``nidreg_cloud_fold_ids``: ``(ids int32 (N,), sizes int64 (num_folds,))`` -- the fold of every point under ``seed`` and how
+        many points each fold holds.  ``cell`` = 0: per-point folds; ``cell`` > 0 (metres): the points of one cube share a fold."""
+        ids = np.empty(self.num_points, dtype=np.int32)
+        sizes = np.zeros(max(int(num_folds), 0), dtype=np.int64)
+        rc = self._lib.nidreg_cloud_fold_ids(self.c, int(seed) & 0xFFFFFFFFFFFFFFFF, float(cell), int(num_folds), ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if ids.size else None,
+                                             sizes.ctypes.data_as(_lib.c_int64_p) if sizes.size else None)
+        _lib.check(rc, "nidreg_cloud_fold_ids")
+        return ids, sizes
+
+    def fold(self, seed, num_folds, fold, complement=False, cell=0.0, return_indices=False):
+        """``nidreg_cloud_fold``: the points whose fold (``fold_ids``) equals ``fold`` -- or, with ``complement``, differs from it -- as
+        a new ``Cloud`` on the same device, in input order, compacted on the GPU.  ``return_indices``: ``(cloud, indices int32
+        ascending)``."""
+        idx = np.empty(max(self.num_points, 1), dtype=np.int32) if return_indices else None
+        out = ctypes.c_void_p()
+        count = ctypes.c_int64(0)
+        rc = self._lib.nidreg_cloud_fold(self.c, int(seed) & 0xFFFFFFFFFFFFFFFF, float(cell), int(num_folds), int(fold), 1 if complement else 0, ctypes.byref(out),
+                                         None if idx is None else idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(count))
+        _lib.check(rc, "nidreg_cloud_fold")
+        sub = Cloud.__new__(Cloud)
+        sub._lib = self._lib
+        sub.c = out
+        sub.device = self.device
+        sub.num_points = int(count.value)
+        return (sub, idx[: sub.num_points].copy()) if return_indices else sub
+
     def get(self):
         """``nidreg_cloud_get``: ``(points (N, 4), intensities (N,))`` as the device holds them."""
         n = ctypes.c_int64(0)

@@ -36,6 +36,8 @@
  *   nidreg_mask_*,           (no reference counterpart: its users edit the PNG or the PLY by hand) image regions and LiDAR
  *   nidreg_cloud_select      ranges left out of the cost: the cull, an eroded 8-bit mask at the point's pixel and a range gate,
  *                            compacted on the device into a new cloud
+ *   nidreg_cloud_fold*       (no reference counterpart) a hashed fold of a cloud, per point or per spatial block, or its complement,
+ *                            compacted on the device into a new cloud: the subsets `evaluate` recalibrates on
  *   nidreg_estimate_directions   vlcal::estimate_direction per keypoint (src/vlcal/common/estimate_fov.cpp:17-34; the loop of
  *                            src/vlcal/common/estimate_pose.cpp:46-51)
  *   nidreg_estimate_rotation_ransac  PoseEstimation::estimate_rotation_ransac, the hypothesis loop and the inlier flags
@@ -252,6 +254,34 @@ int nidreg_cloud_select(const nidreg_cloud* cloud, int model_id, const double* i
 /* what became of the source's points, for a cloud nidreg_cloud_select made: counts3 = {kept by the cull, of those removed by the mask,
  * of the rest removed by the range gate}; the cloud's size is [0] - [1] - [2].  NIDREG_ERR_INVALID for any other cloud. */
 int nidreg_cloud_select_counts(const nidreg_cloud* selected, int64_t* counts3);
+
+/* Folds of a cloud (no counterpart in the reference): a fold of a device-resident cloud, or its complement, as a new cloud on the
+ * same device, without a host round trip -- what recalibrating on subsets of the data (jackknife, held-out subsets) needs.
+ *
+ * The fold of point i is a function of (seed, cell, num_folds) and of the point alone, in integer arithmetic modulo 2^64 apart from
+ * the one division below:
+ *   mix64(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *   key        cell == 0 (per-point folds): i.
+ *              cell > 0 (spatial blocks: the points of one cell-metre cube share a fold): c_a = floor(p_a / cell) per axis in double
+ *              (a true division, then floor); if x, y, z are finite and every c_a lies in [-2^20, 2^20):
+ *              (c_x + 2^20) | (c_y + 2^20) << 21 | (c_z + 2^20) << 42 (the integrator's packing); otherwise 2^63 | i (the point is
+ *              folded on its own)
+ *   fold       h = mix64(seed + 0x9E3779B97F4A7C15 * (key + 1));  fold = ((h >> 32) * num_folds) >> 32
+ * (seed = 0, key = 0, 1, 2: h = 0xE220A8397B1DCDAF, 0x6E789E6AA1B965F4, 0x06C45D188009454F.)
+ *
+ * nidreg_cloud_fold_ids: the fold of every point to folds_out (n words; may be NULL only for an empty cloud) and the folds' sizes to
+ * sizes_out (num_folds words, nullable).
+ * nidreg_cloud_fold: the points whose fold equals `fold` (complement == 0) or differs from it (complement != 0) become a new cloud
+ * *out (nidreg_cloud_destroy) in input order, points and intensities copied byte for byte; their ascending indices go to indices_out
+ * (nullable; capacity = the cloud's size) and their number to *count_out.  An empty result is a valid empty cloud.  The source is
+ * not modified.  nidreg_cloud_select_counts refuses *out: it is not a selection.
+ * Deterministic, no atomics: a flag pass with wave64 ballots, then nidreg_cloud_select's exclusive scan and gather; the sizes come
+ * from per-workgroup ballots and sums, reduced in a fixed order.
+ * NIDREG_ERR_INVALID before any device call: a NULL cloud / out / count_out / folds_out (with points), num_folds outside
+ * [1, NIDREG_FOLD_MAX], fold outside [0, num_folds), a negative, NaN or infinite cell. */
+#define NIDREG_FOLD_MAX 1024
+int nidreg_cloud_fold_ids(const nidreg_cloud* cloud, uint64_t seed, double cell, int num_folds, int32_t* folds_out, int64_t* sizes_out);
+int nidreg_cloud_fold(const nidreg_cloud* cloud, uint64_t seed, double cell, int num_folds, int fold, int complement, nidreg_cloud** out, int32_t* indices_out, int64_t* count_out);
 
 /* NIDCost::operator(): cost (+ gradient when grad7 != NULL) at se3 = [qx qy qz qw tx ty tz] */
 int nidreg_eval(nidreg_handle* h, const double* se3, double* cost, double* grad7);
