@@ -77,7 +77,7 @@ EXPORTS = [
     "nidreg_estimate_camera_fov", "nidreg_rccl_unique_id", "nidreg_shard_comm_init", "nidreg_shard_attach_rccl", "nidreg_kernel_build",
     "nidreg_estimate_directions", "nidreg_ransac_sample_pairs", "nidreg_estimate_rotation_ransac",
     "nidreg_integrator_create", "nidreg_integrator_insert", "nidreg_integrator_insert_f32", "nidreg_integrator_insert_cloud2", "nidreg_integrator_size", "nidreg_integrator_get", "nidreg_integrator_info",
-    "nidreg_integrator_destroy",
+    "nidreg_integrator_destroy", "nidreg_integrator_insert_las", "nidreg_integrator_las_timing", "nidreg_lzf_decompress",
     "nidreg_odom_create", "nidreg_odom_destroy", "nidreg_odom_knn_covariances", "nidreg_odom_covariances", "nidreg_odom_model_insert", "nidreg_odom_model_info", "nidreg_odom_model_get", "nidreg_odom_set_lru", "nidreg_odom_lru_info",
     "nidreg_odom_set_source", "nidreg_odom_linearize", "nidreg_odom_error", "nidreg_odom_correspondences", "nidreg_odom_deskew_insert",
     "nidreg_features_detect", "nidreg_features_match",
@@ -163,6 +163,10 @@ def load():
     lib.nidreg_integrator_insert_f32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64]
     lib.nidreg_integrator_insert_cloud2.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                     ctypes.c_int32, c_int64_p]
+    lib.nidreg_integrator_insert_las.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_double_p, c_double_p, c_double_p, ctypes.c_int32,
+                                                 ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32, c_int64_p]
+    lib.nidreg_integrator_las_timing.argtypes = [c_double_p]
+    lib.nidreg_lzf_decompress.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, c_int64_p]
     lib.nidreg_integrator_size.argtypes = [ctypes.c_void_p, c_int64_p]
     lib.nidreg_integrator_get.argtypes = [ctypes.c_void_p, c_float_p, c_int64_p]
     lib.nidreg_integrator_info.argtypes = [ctypes.c_void_p, c_int64_p]

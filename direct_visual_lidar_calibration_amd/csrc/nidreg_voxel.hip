@@ -2,11 +2,14 @@
 // (src/vlcal/preprocess/static_point_cloud_integrator.cpp:25-62) on the device (kernels: nid_voxel_kernels.hpp).  The handle owns
 // the hash table, one frame's upload (and, for the PointCloud2 route, its decoded form) and the per-point slot scratch of one chunk: device memory is O(occupied voxels + one frame).
 #include "nid_voxel_kernels.hpp"
+#include "nid_las_kernels.hpp"
+#include "nid_lzf_host.hpp"
 #include "nid_launch.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -289,6 +292,86 @@ int nidreg_integrator_insert_cloud2(nidreg_integrator* h, const void* data, int6
     cloud2_launch<kPcFloat64>(c, intensity_datatype, d_pts, d_int);
   HIP_TRY(hipGetLastError());
   return integrator_insert_staged(h, who, num_points, num_skipped);
+}
+
+// host wall-clock milliseconds of the calling thread's last nidreg_integrator_insert_las: checks + allocation + upload, decode kernel
+// (launch to idle), the integrator's passes
+static thread_local double g_las_ms[3] = {0.0, 0.0, 0.0};
+static double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+
+// LAS point formats 0..10: the base record length, and where the red channel lies (0 = the format has no RGB)
+static const int kLasBaseLength[11] = {20, 28, 26, 34, 57, 63, 30, 36, 38, 59, 67};
+static const int kLasRgbOffset[11] = {0, 0, 20, 28, 0, 28, 0, 30, 30, 0, 30};
+
+int nidreg_integrator_insert_las(nidreg_integrator* h, const void* records, int64_t num_points, int32_t record_length, int32_t point_format, const double* scale3, const double* offset3,
+                                 const double* origin3, int32_t intensity_source, const uint64_t* exclude_classes4, int32_t keep_withheld, int64_t* num_skipped) {
+  const std::string who = "nidreg_integrator_insert_las";
+  if (num_skipped) *num_skipped = 0;
+  g_las_ms[0] = g_las_ms[1] = g_las_ms[2] = 0.0;
+  auto t0 = std::chrono::steady_clock::now();
+  // every check of the arguments themselves comes before the handle is looked at, and all of it before the device is touched
+  if (point_format < 0 || point_format > 10) return fail(NIDREG_ERR_INVALID, who + ": point formats 0..10 are read, got " + std::to_string(point_format));
+  if (record_length < kLasBaseLength[point_format] || record_length > 65535)
+    return fail(NIDREG_ERR_INVALID, who + ": record_length " + std::to_string(record_length) + " is outside " + std::to_string(kLasBaseLength[point_format]) + "..65535, the range of point format " +
+                                        std::to_string(point_format));
+  if (!scale3 || !offset3 || !origin3) return fail(NIDREG_ERR_INVALID, who + ": null scale3, offset3 or origin3");
+  for (int a = 0; a < 3; a++) {
+    if (!std::isfinite(scale3[a]) || scale3[a] == 0.0) return fail(NIDREG_ERR_INVALID, who + ": a scale must be finite and not zero, got " + std::to_string(scale3[a]));
+    if (!std::isfinite(offset3[a]) || !std::isfinite(origin3[a])) return fail(NIDREG_ERR_INVALID, who + ": a non-finite offset or origin");
+  }
+  if (intensity_source != 0 && intensity_source != 1) return fail(NIDREG_ERR_INVALID, who + ": intensity_source must be 0 (intensity) or 1 (rgb), got " + std::to_string(intensity_source));
+  if (intensity_source == 1 && !kLasRgbOffset[point_format]) return fail(NIDREG_ERR_INVALID, who + ": rgb intensity asked of point format " + std::to_string(point_format) + ", which has no RGB channels");
+  if (num_points < 0 || (num_points > 0 && !records)) return fail(NIDREG_ERR_INVALID, who + ": negative num_points or null records");
+  // the handle, the upload of the records as they lie in the file and the frame's room: the PointCloud2 route's first half, told
+  // the truth about the record -- three 4-byte coordinates at 0, 4, 8 and a 16-bit intensity at 12
+  VoxCloud2 c;
+  double4* d_pts = nullptr;
+  double* d_int = nullptr;
+  if (const int rc = integrator_stage_cloud2(h, who.c_str(), records, num_points, record_length, 0, 4, 8, kPcFloat32, 12, kPcUint16, &c, &d_pts, &d_int)) return rc;
+  if (num_points == 0) return NIDREG_OK;
+  g_las_ms[0] = ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  const bool modern = point_format >= 6;
+  VoxLas las;
+  las.raw = c.raw, las.n = c.n, las.step = c.step;
+  las.o_rgb = intensity_source == 1 ? kLasRgbOffset[point_format] : -1;
+  las.o_class = modern ? 16 : 15;
+  las.class_bits = modern ? 0xffu : 0x1fu;
+  las.withheld_drop = keep_withheld ? 0u : (modern ? 0x04u : 0x80u);
+  las.sx = scale3[0], las.sy = scale3[1], las.sz = scale3[2];
+  las.ox = offset3[0], las.oy = offset3[1], las.oz = offset3[2];
+  las.gx = origin3[0], las.gy = origin3[1], las.gz = origin3[2];
+  vox_u64 m[4] = {0, 0, 0, 0};
+  if (exclude_classes4)
+    for (int k = 0; k < 4; k++) m[k] = vox_u64(exclude_classes4[k]);
+  const dim3 grid(vox_grid(num_points)), block(kVoxThreads);
+  if (record_length <= kVoxStageStep)
+    hipLaunchKernelGGL((k_vox_decode_las<true>), grid, block, 0, nullptr, las, m[0], m[1], m[2], m[3], d_pts, d_int);
+  else
+    hipLaunchKernelGGL((k_vox_decode_las<false>), grid, block, 0, nullptr, las, m[0], m[1], m[2], m[3], d_pts, d_int);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(nullptr));  // (the check pass that follows reads its counters back, so the insert waits here anyway: this only splits the clock)
+  g_las_ms[1] = ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  const int rc = integrator_insert_staged(h, who.c_str(), num_points, num_skipped);
+  g_las_ms[2] = ms_since(t0);
+  return rc;
+}
+
+int nidreg_integrator_las_timing(double* ms3) {
+  if (!ms3) return fail(NIDREG_ERR_INVALID, "nidreg_integrator_las_timing: null ms3");
+  for (int k = 0; k < 3; k++) ms3[k] = g_las_ms[k];
+  return NIDREG_OK;
+}
+
+int nidreg_lzf_decompress(const uint8_t* in, int64_t in_size, uint8_t* out, int64_t out_size, int64_t* written) {
+  if (written) *written = 0;
+  if (in_size < 0 || out_size < 0 || (in_size > 0 && !in) || (out_size > 0 && !out)) return fail(NIDREG_ERR_INVALID, "nidreg_lzf_decompress: negative size or null buffer");
+  size_t got = 0;
+  std::string reason;
+  const bool ok = nidlzf::decompress(in, size_t(in_size), out, size_t(out_size), got, reason);
+  if (written) *written = int64_t(got);
+  return ok ? NIDREG_OK : fail(NIDREG_ERR_INVALID, "nidreg_lzf_decompress: " + reason);
 }
 
 int nidreg_integrator_size(nidreg_integrator* h, int64_t* num_voxels) {

@@ -203,8 +203,9 @@ def read_pcd(path):
     """The x y z (and, if present, intensity) fields of a PCD file, ``DATA ascii`` or ``DATA binary`` -- what
     ``pcl::io::load`` into a ``PointXYZI`` cloud keeps (preprocess_map.cpp:129-131).  Returns what ``read_ply_float32`` returns:
     ``(xyz (n, 3), intensities (n,))`` float32 (views over one buffer for binary files; zeros where the file has no intensity
-    field).  The four fields must be ``F 4``; other fields are skipped by their SIZE x COUNT.  ``binary_compressed`` and other
-    field types are refused with a ValueError that names what was found."""
+    field).  The four fields must be ``F 4``; other fields are skipped by their SIZE x COUNT.  ``DATA binary_compressed`` (one LZF
+    stream of per-field planes, ``_pcd_compressed_columns``) is read too.  Other data formats and field types are refused with a
+    ValueError that names what was found."""
     with open(path, "rb") as f:
         data = f.read()
     head = {}
@@ -232,8 +233,8 @@ def read_pcd(path):
     else:
         raise ValueError(f"{path}: PCD header without POINTS or WIDTH / HEIGHT")
     fmt = head["DATA"][0].lower() if head["DATA"] else ""
-    if fmt not in ("ascii", "binary"):
-        raise ValueError(f"{path}: unsupported PCD data format '{fmt}' (ascii and binary are read)")
+    if fmt not in ("ascii", "binary", "binary_compressed"):
+        raise ValueError(f"{path}: unsupported PCD data format '{fmt}' (ascii, binary and binary_compressed are read)")
     wanted = [k for k in ("x", "y", "z", "intensity") if k in fields]
     for k in ("x", "y", "z"):
         if k not in fields:
@@ -248,6 +249,8 @@ def read_pcd(path):
             raise ValueError(f"{path}: truncated PCD point data")
         rec = np.frombuffer(data, dtype=dt, count=n, offset=pos)
         cols = {k: rec[f"f{fields.index(k)}"] for k in wanted}
+    elif fmt == "binary_compressed":
+        cols = _pcd_compressed_columns(path, data, pos, n, fields, sizes, counts, wanted)
     else:
         first = np.concatenate([[0], np.cumsum(counts)])  # first token of every field
         rows = [ln.split() for ln in data[pos:].decode("ascii", "replace").splitlines() if ln.strip()][:n]
@@ -258,6 +261,113 @@ def read_pcd(path):
     xyz[:, 0], xyz[:, 1], xyz[:, 2] = cols["x"], cols["y"], cols["z"]
     inten = np.ascontiguousarray(cols["intensity"]) if "intensity" in cols else np.zeros(n, dtype=np.float32)
     return xyz, inten
+
+
+def lzf_decompress(stream, out_size):
+    """``nidreg_lzf_decompress`` (host only, csrc/nid_lzf_host.hpp): the LZF stream ``stream`` into at most ``out_size`` bytes, as a
+    uint8 array of the bytes produced.  ``ValueError`` with the input offset for a stream that ends inside a token, refers to before
+    the output or overruns ``out_size``."""
+    import ctypes
+
+    from . import _lib
+
+    lib = _lib.load()
+    src = np.frombuffer(bytes(stream), dtype=np.uint8)
+    out = np.empty(max(int(out_size), 1), dtype=np.uint8)
+    written = ctypes.c_int64()
+    rc = lib.nidreg_lzf_decompress(src.ctypes.data if src.size else None, src.size, out.ctypes.data, int(out_size), ctypes.byref(written))
+    if rc == _lib.NIDREG_ERR_INVALID:
+        raise ValueError(_lib.last_error())
+    _lib.check(rc, "nidreg_lzf_decompress")
+    return out[: int(written.value)]
+
+
+def _pcd_compressed_columns(path, data, pos, n, fields, sizes, counts, wanted):
+    """The wanted columns of a ``DATA binary_compressed`` body: a u32 compressed size, a u32 uncompressed size, then one LZF stream
+    whose output is one plane per field in header order, ``n x SIZE x COUNT`` bytes each (what
+    ``pcl::io::savePCDFileBinaryCompressed`` writes).  Unpinned against PCL / liblzf and real files."""
+    if pos + 8 > len(data):
+        raise ValueError(f"{path}: truncated PCD point data (binary_compressed: no size words)")
+    comp, uncomp = struct.unpack_from("<II", data, pos)
+    widths = [s * c for s, c in zip(sizes, counts)]
+    if uncomp != n * sum(widths):
+        raise ValueError(f"{path}: binary_compressed body says {uncomp} uncompressed bytes; {n} points of {sum(widths)} bytes are {n * sum(widths)}")
+    if pos + 8 + comp > len(data):
+        raise ValueError(f"{path}: truncated PCD point data (binary_compressed: {comp} compressed bytes announced, {len(data) - pos - 8} present)")
+    try:
+        plain = lzf_decompress(data[pos + 8 : pos + 8 + comp], uncomp)
+    except ValueError as e:
+        raise ValueError(f"{path}: binary_compressed body does not decode: {e}") from None
+    if plain.size != uncomp:
+        raise ValueError(f"{path}: binary_compressed body decodes to {plain.size} bytes, {uncomp} announced")
+    starts = np.concatenate([[0], np.cumsum(widths)]) * n
+    return {k: np.array(plain[starts[fields.index(k)] : starts[fields.index(k)] + 4 * n].view("<f4")) for k in wanted}  # (copies: a plane may start off a 4-byte boundary)
+
+
+# --------------------------------------------------------------------------------------------- LAS
+LAS_BASE_LENGTH = (20, 28, 26, 34, 57, 63, 30, 36, 38, 59, 67)  # point formats 0..10
+LAS_RGB_OFFSET = {2: 20, 3: 28, 5: 28, 7: 30, 8: 30, 10: 30}  # byte of the u16 red channel; the other formats have no colour
+
+
+def read_las_header(path):
+    """The public header block of an ASPRS LAS 1.0 - 1.4 file, little-endian, as a dict: ``version`` (major, minor),
+    ``header_size``, ``point_offset``, ``point_format``, ``record_length``, ``num_points`` (the 64-bit count of a 1.4 header when it
+    is non-zero, else the legacy count), ``scale`` / ``offset`` / ``min`` / ``max`` (three floats each) and ``file_size``.  Read
+    from the public format description; unpinned against laspy / PDAL and real files.  ``ValueError`` that names what was found for
+    a wrong signature, a version other than 1.0 - 1.4, a compressed file (LAZ), a point format above 10, a record shorter than its
+    format, a zero or non-finite scale, a non-finite offset, a header or point offset past the file and a truncated point block."""
+    size = os.path.getsize(path)
+    with open(path, "rb") as f:
+        head = f.read(375)
+    if len(head) < 4 or head[:4] != b"LASF":
+        raise ValueError(f"{path}: not a LAS file (signature {head[:4]!r}, 'LASF' expected)")
+    if len(head) < 227:
+        raise ValueError(f"{path}: truncated LAS header ({len(head)} bytes; the public header block is at least 227)")
+    major, minor = head[24], head[25]
+    if major != 1 or minor > 4:
+        raise ValueError(f"{path}: LAS version {major}.{minor}; 1.0 to 1.4 are read")
+    header_size, point_offset = struct.unpack_from("<HI", head, 94)
+    fmt_byte, record_length, legacy_count = struct.unpack_from("<BHI", head, 104)
+    if fmt_byte & 0xC0:
+        raise ValueError(f"{path}: compressed LAS (LAZ) is not read (point format byte {fmt_byte:#04x})")
+    if fmt_byte > 10:
+        raise ValueError(f"{path}: LAS point format {fmt_byte}; formats 0 to 10 are read")
+    if record_length < LAS_BASE_LENGTH[fmt_byte]:
+        raise ValueError(f"{path}: LAS record length {record_length} is below the {LAS_BASE_LENGTH[fmt_byte]} bytes of point format {fmt_byte}")
+    scale = struct.unpack_from("<3d", head, 131)
+    offset = struct.unpack_from("<3d", head, 155)
+    bounds = struct.unpack_from("<6d", head, 179)  # max x, min x, max y, min y, max z, min z
+    if any(not np.isfinite(s) or s == 0.0 for s in scale):
+        raise ValueError(f"{path}: LAS scale {scale} has a zero or non-finite factor")
+    if any(not np.isfinite(o) for o in offset):
+        raise ValueError(f"{path}: LAS offset {offset} is not finite")
+    if header_size < 227 or header_size > size:
+        raise ValueError(f"{path}: LAS header size {header_size} lies outside the file ({size} bytes; at least 227)")
+    if point_offset < header_size or point_offset > size:
+        raise ValueError(f"{path}: LAS offset to point data {point_offset} lies outside the file ({size} bytes, header {header_size})")
+    count = legacy_count
+    if minor >= 4 and header_size >= 375 and len(head) >= 255:
+        count64 = struct.unpack_from("<Q", head, 247)[0]
+        if count64:
+            count = count64
+    if point_offset + count * record_length > size:
+        raise ValueError(f"{path}: truncated LAS point data ({count} records of {record_length} bytes from offset {point_offset} need {point_offset + count * record_length} bytes, the file has {size})")
+    return {"version": (int(major), int(minor)), "header_size": int(header_size), "point_offset": int(point_offset), "point_format": int(fmt_byte), "record_length": int(record_length),
+            "num_points": int(count), "scale": tuple(scale), "offset": tuple(offset), "min": (bounds[1], bounds[3], bounds[5]), "max": (bounds[0], bounds[2], bounds[4]), "file_size": int(size)}
+
+
+def read_las_chunks(path, header, chunk_points=1 << 23):
+    """The point records of a LAS file as ``(chunk_points x record_length,)`` uint8 arrays, one ``np.fromfile`` per chunk (not a
+    memmap: no page faults inside the upload): host memory is one chunk, whatever the file size."""
+    if chunk_points < 1:
+        raise ValueError("read_las_chunks: chunk_points must be positive")
+    step, n = header["record_length"], header["num_points"]
+    for first in range(0, n, int(chunk_points)):
+        m = min(int(chunk_points), n - first)
+        raw = np.fromfile(path, dtype=np.uint8, count=m * step, offset=header["point_offset"] + first * step)
+        if raw.size != m * step:
+            raise ValueError(f"{path}: truncated LAS point data (records {first}..{first + m})")
+        yield raw
 
 
 # --------------------------------------------------------------------------------------------- PNG

@@ -117,6 +117,32 @@ class StaticPointCloudIntegrator:
         _check(rc, "nidreg_integrator_insert_cloud2")
         return int(skipped.value)
 
+    def insert_las(self, records, record_length, point_format, scale, offset, origin=(0.0, 0.0, 0.0), intensity="intensity", exclude_classes=(), keep_withheld=False):
+        """Point records of an ASPRS LAS file as they lie in the file (``dataset.read_las_chunks``): ``records`` a contiguous uint8
+        array of whole ``record_length``-byte records of ``point_format`` 0..10, uploaded as they are and decoded on the GPU --
+        ``(int32 * scale + offset) - origin`` in fp64, so a georeferenced map is recentred before anything is narrowed to float32.
+        ``intensity``: ``"intensity"`` (the 16-bit field) or ``"rgb"`` (77 R + 150 G + 29 B; formats with colour only).  Points
+        whose class is in ``exclude_classes`` (0..255) and, unless ``keep_withheld``, withheld points are skipped like non-finite
+        PointCloud2 points: they take a sequence number and are counted in the return value."""
+        records = np.ascontiguousarray(records, dtype=np.uint8).reshape(-1)
+        step = int(record_length)
+        if step < 1 or records.size % step:
+            raise ValueError(f"insert_las: {records.size} bytes are not whole records of {step} bytes")
+        if intensity not in ("intensity", "rgb"):
+            raise ValueError(f"insert_las: intensity must be 'intensity' or 'rgb', got {intensity!r}")
+        mask = (ctypes.c_uint64 * 4)()
+        for c in exclude_classes:
+            if not 0 <= int(c) <= 255:
+                raise ValueError(f"insert_las: class {c} is outside 0..255")
+            mask[int(c) >> 6] |= 1 << (int(c) & 63)
+        n = records.size // step
+        triples = [(ctypes.c_double * 3)(*[float(v) for v in t]) for t in (scale, offset, origin)]
+        skipped = ctypes.c_int64()
+        rc = self._lib.nidreg_integrator_insert_las(self._h, records.ctypes.data if n else None, n, step, int(point_format), triples[0], triples[1], triples[2],
+                                                    1 if intensity == "rgb" else 0, mask, 1 if keep_withheld else 0, ctypes.byref(skipped))
+        _check(rc, "nidreg_integrator_insert_las")
+        return int(skipped.value)
+
     def size(self):
         m = ctypes.c_int64()
         _check(self._lib.nidreg_integrator_size(self._h, ctypes.byref(m)), "nidreg_integrator_size")

@@ -480,6 +480,27 @@ void nidreg_splat_destroy(nidreg_splat* s);
  *                              device call: a field outside the record, point_step out of range, another datatype, NULL data with
  *                              num_points > 0, num_points < 0.  num_points == 0 is a valid insert.  Device memory: the raw frame and
  *                              40 bytes per point of it.
+ *   nidreg_integrator_insert_las  the point records of an ASPRS LAS 1.0 - 1.4 file as they lie in the file (dataset.read_las_header says
+ *                              where): num_points records of record_length bytes of point_format 0..10 (base lengths 20, 28, 26, 34,
+ *                              57, 63, 30, 36, 38, 59, 67; a longer record carries extra bytes), uploaded once and decoded on the GPU
+ *                              (csrc/nid_las_kernels.hpp).  Coordinate = (double(int32) * scale + offset) - origin, three separately
+ *                              rounded fp64 operations: the file's own definition, then the recentring of a georeferenced map before
+ *                              anything is narrowed to float32.  intensity_source 0: the 16-bit intensity; 1: 77 R + 150 G + 29 B of
+ *                              the 16-bit colour channels (formats 2, 3, 5, 7, 8, 10 only).  exclude_classes4 (nullable): 256 bits,
+ *                              bit c set = points of class c are dropped (the class is 5 bits in formats 0 - 5, 8 bits in 6 - 10);
+ *                              withheld points are dropped unless keep_withheld.  A dropped point is SKIPPED the way a non-finite
+ *                              PointCloud2 point is: counted in *num_skipped (nullable), and it still takes its sequence number.
+ *                              A kept point outside the packed-key limit refuses the whole chunk.  NIDREG_ERR_INVALID before any
+ *                              device call, the arguments before the handle: a format outside 0..10, a record_length below the
+ *                              format's base or above 65535, a NULL scale3 / offset3 / origin3, a scale that is zero or non-finite, a
+ *                              non-finite offset or origin, another intensity_source, rgb asked of a format without it, NULL records
+ *                              with num_points > 0, num_points < 0, a NULL integrator.  UNPINNED against laspy / PDAL and real files.
+ *   nidreg_integrator_las_timing  host wall-clock milliseconds of the calling thread's last nidreg_integrator_insert_las: [0] checks,
+ *                              allocation and upload, [1] the decode kernel, launch to idle, [2] the integrator's passes.
+ *   nidreg_lzf_decompress      host only (csrc/nid_lzf_host.hpp): the LZF stream of a PCD file's `DATA binary_compressed` body into
+ *                              out_size bytes; *written (nullable) = bytes produced.  Input that ends inside a token, a reference to
+ *                              before the output and an output overrun are NIDREG_ERR_INVALID, the input offset in
+ *                              nidreg_last_error().  UNPINNED against liblzf / PCL and real files.
  *   nidreg_integrator_size     voxelgrid.size()
  *   nidreg_integrator_get      get_points (:49-62): num_voxels records of 16 bytes, float x y z intensity = `cast<float>()` of the
  *                              entry (the PLY record: feeds nidreg_cloud_create_f32 and a PLY writer without a repack); seq
@@ -500,6 +521,11 @@ int nidreg_integrator_insert(nidreg_integrator* h, const double* points, int64_t
 int nidreg_integrator_insert_f32(nidreg_integrator* h, const float* points, int64_t point_stride, const float* intensities, int64_t intensity_stride, int64_t n);
 int nidreg_integrator_insert_cloud2(nidreg_integrator* h, const void* data, int64_t num_points, int32_t point_step, int32_t x_offset, int32_t y_offset, int32_t z_offset, int32_t xyz_datatype,
                                     int32_t intensity_offset, int32_t intensity_datatype, int64_t* num_skipped);
+int nidreg_integrator_insert_las(nidreg_integrator* h, const void* records, int64_t num_points, int32_t record_length, int32_t point_format, const double* scale3, const double* offset3,
+                                 const double* origin3, int32_t intensity_source /* 0 = intensity, 1 = rgb */, const uint64_t* exclude_classes4 /* nullable: 256 bits, bit c = drop class c */,
+                                 int32_t keep_withheld, int64_t* num_skipped);
+int nidreg_integrator_las_timing(double* ms3);
+int nidreg_lzf_decompress(const uint8_t* in, int64_t in_size, uint8_t* out, int64_t out_size, int64_t* written);
 int nidreg_integrator_size(nidreg_integrator* h, int64_t* num_voxels);
 int nidreg_integrator_get(nidreg_integrator* h, float* records16 /* num_voxels x {x, y, z, intensity} */, int64_t* seq /* optional, may be NULL */);
 int nidreg_integrator_info(nidreg_integrator* h, int64_t* info4);
