@@ -166,7 +166,7 @@ hipError_t build_records_device(
   DeviceBuf recs;
   void* d_recs = nullptr;
   std::vector<int> first(size_t(NG) + 2, -1);
-  const unsigned grid = unsigned((n + 255) / 256);
+  const unsigned grid = blocks_for(n, 256);
   long long kept = 0;
   int rec64 = 0;
   gcount.assign(size_t(NG) + 1, 0);
@@ -198,8 +198,7 @@ hipError_t build_records_device(
     CARVE(d_first, int*, 4096);
     BUILD_TRY(hipMemsetAsync(d_first, 0xff, (size_t(NG) + 1) * sizeof(int), stream));
     BUILD_TRY(hipMemsetAsync(d_first + NG + 1, 0, sizeof(int), stream));
-    hipLaunchKernelGGL(k_build_keys, dim3(grid), dim3(256), 0, stream, d_pts, d_intensities, d_keep, n, Bsrc, d_lut, GW, input_order ? 1 : 0, d_keys, d_idx, d_first + NG + 1);
-    BUILD_TRY(hipGetLastError());
+    BUILD_TRY(launch(k_build_keys, grid, 256, 0, stream, d_pts, d_intensities, d_keep, n, Bsrc, d_lut, GW, input_order ? 1 : 0, d_keys, d_idx, d_first + NG + 1));
     // key = [group : 23][column : 9][Morton code : 32], or [group : 23][input index : 41] to keep the caller's order inside
     // a group; removed points carry all-ones and sort last
     // Only the key bits that can differ are sorted: 41 low bits, the group's bits, and ONE bit above them -- 0 in every real key, 1 in
@@ -211,8 +210,7 @@ hipError_t build_records_device(
     BUILD_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, size_t(n), 0, end_bit, stream));
     CARVE(d_tmp, void*, tmp_bytes > 0 ? tmp_bytes : 256);
     BUILD_TRY(rocprim::radix_sort_pairs(d_tmp, tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, size_t(n), 0, end_bit, stream));
-    hipLaunchKernelGGL(k_build_bounds, dim3(grid), dim3(256), 0, stream, d_keys2, n, NG, d_first);
-    BUILD_TRY(hipGetLastError());
+    BUILD_TRY(launch(k_build_bounds, grid, 256, 0, stream, d_keys2, n, NG, d_first));
     BUILD_TRY(hipMemcpyAsync(first.data(), d_first, (size_t(NG) + 2) * sizeof(int), hipMemcpyDeviceToHost, stream));
     BUILD_TRY(hipStreamSynchronize(stream));
     kept = first[size_t(NG)] >= 0 ? first[size_t(NG)] : n;
@@ -232,12 +230,11 @@ hipError_t build_records_device(
     BUILD_TRY(recs.alloc(size_t(kept > 0 ? kept : 1) * rec_bytes + 64));
     d_recs = recs.as<void>();
     if (kept > 0) {
-      const unsigned g2 = unsigned((kept + 255) / 256);
+      const unsigned g2 = blocks_for(kept, 256);
       if (rec64)
-        hipLaunchKernelGGL(k_build_gather<Rec64>, dim3(g2), dim3(256), 0, stream, d_pts, d_intensities, d_idx2, kept, Bsrc, d_lut, static_cast<Rec64*>(d_recs));
+        BUILD_TRY(launch(k_build_gather<Rec64>, g2, 256, 0, stream, d_pts, d_intensities, d_idx2, kept, Bsrc, d_lut, static_cast<Rec64*>(d_recs)));
       else
-        hipLaunchKernelGGL(k_build_gather<Rec32>, dim3(g2), dim3(256), 0, stream, d_pts, d_intensities, d_idx2, kept, Bsrc, d_lut, static_cast<Rec32*>(d_recs));
-      BUILD_TRY(hipGetLastError());
+        BUILD_TRY(launch(k_build_gather<Rec32>, g2, 256, 0, stream, d_pts, d_intensities, d_idx2, kept, Bsrc, d_lut, static_cast<Rec32*>(d_recs)));
       BUILD_TRY(hipStreamSynchronize(stream));
     }
   }
@@ -275,8 +272,7 @@ __global__ __launch_bounds__(256) void k_build_bin_image(const unsigned char* __
 
 hipError_t build_bin_image_device(const void* d_src, int is_f64, long long row_stride, int W, int H, int B, const uint16_t* d_lut, int pitch, int nstrips, uint8_t* d_img, hipStream_t stream) {
   const long long total = (long long)pitch * nstrips * 4;
-  hipLaunchKernelGGL(k_build_bin_image, dim3(unsigned((total + 255) / 256)), dim3(256), 0, stream, static_cast<const unsigned char*>(d_src), is_f64, row_stride, W, H, B, d_lut, pitch, nstrips * 4, d_img);
-  return hipGetLastError();
+  return launch(k_build_bin_image, blocks_for(total, 256), 256, 0, stream, static_cast<const unsigned char*>(d_src), is_f64, row_stride, W, H, B, d_lut, pitch, nstrips * 4, d_img);
 }
 
 // which of the B bins the n device-resident values v occupy (bins > 256 on a device-resident cloud: nidreg_plan.hip resolve_wide_bins)
@@ -287,8 +283,7 @@ hipError_t mark_bins_device(const double* d_v, long long n, int B, unsigned char
   unsigned char* d_used = used.as<unsigned char>();
   e = hipMemset(d_used, 0, size_t(B));
   if (e == hipSuccess && n > 0) {
-    hipLaunchKernelGGL(k_mark_bins, dim3(unsigned((n + 255) / 256)), dim3(256), 0, hipStream_t(nullptr), d_v, n, B, d_used);
-    e = hipGetLastError();
+    e = launch(k_mark_bins, blocks_for(n, 256), 256, 0, nullptr, d_v, n, B, d_used);
   }
   if (e == hipSuccess) e = hipMemcpy(used_host, d_used, size_t(B), hipMemcpyDeviceToHost);
   return e;
@@ -326,13 +321,11 @@ __global__ __launch_bounds__(256) void k_cloud_widen(const unsigned char* __rest
 hipError_t widen_cloud_device(const void* d_src, long long pt_off, long long pt_stride, long long in_off, long long in_stride, long long n, double* d_pts, double* d_int,
                               hipStream_t stream) {
   if (n <= 0) return hipSuccess;
-  const unsigned grid = unsigned((n + 255) / 256);
+  const unsigned grid = blocks_for(n, 256);
   const unsigned char* src = static_cast<const unsigned char*>(d_src);
   if (pt_off == 0 && pt_stride == 16 && in_off == 12 && in_stride == 16 && (reinterpret_cast<uintptr_t>(src) & 15) == 0)
-    hipLaunchKernelGGL(k_cloud_widen<true>, dim3(grid), dim3(256), 0, stream, src, pt_off, pt_stride, in_off, in_stride, n, d_pts, d_int);
-  else
-    hipLaunchKernelGGL(k_cloud_widen<false>, dim3(grid), dim3(256), 0, stream, src, pt_off, pt_stride, in_off, in_stride, n, d_pts, d_int);
-  return hipGetLastError();
+    return launch(k_cloud_widen<true>, grid, 256, 0, stream, src, pt_off, pt_stride, in_off, in_stride, n, d_pts, d_int);
+  return launch(k_cloud_widen<false>, grid, 256, 0, stream, src, pt_off, pt_stride, in_off, in_stride, n, d_pts, d_int);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -363,20 +356,18 @@ hipError_t equalize_intensities_device(double* d_intensities, long long n, hipSt
   unsigned long long *d_keys = nullptr, *d_keys2 = nullptr;
   unsigned int *d_idx = nullptr, *d_idx2 = nullptr;
   size_t tmp_bytes = 0;
-  const unsigned grid = unsigned((n + 255) / 256);
+  const unsigned grid = blocks_for(n, 256);
   BUILD_TRY(keys.alloc(size_t(n) * 8));
   BUILD_TRY(keys2.alloc(size_t(n) * 8));
   BUILD_TRY(idx.alloc(size_t(n) * 4));
   BUILD_TRY(idx2.alloc(size_t(n) * 4));
   d_keys = keys.as<unsigned long long>(), d_keys2 = keys2.as<unsigned long long>();
   d_idx = idx.as<unsigned int>(), d_idx2 = idx2.as<unsigned int>();
-  hipLaunchKernelGGL(k_eq_keys, dim3(grid), dim3(256), 0, stream, d_intensities, n, d_keys, d_idx);
-  BUILD_TRY(hipGetLastError());
+  BUILD_TRY(launch(k_eq_keys, grid, 256, 0, stream, d_intensities, n, d_keys, d_idx));
   BUILD_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, size_t(n), 0, 64, stream));
   BUILD_TRY(tmp.alloc(tmp_bytes));
   BUILD_TRY(rocprim::radix_sort_pairs(tmp.as<void>(), tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, size_t(n), 0, 64, stream));
-  hipLaunchKernelGGL(k_eq_scatter, dim3(grid), dim3(256), 0, stream, d_idx2, n, d_intensities);
-  BUILD_TRY(hipGetLastError());
+  BUILD_TRY(launch(k_eq_scatter, grid, 256, 0, stream, d_idx2, n, d_intensities));
   BUILD_TRY(hipStreamSynchronize(stream));
 done:
   return e;

@@ -174,8 +174,8 @@ inline CamParams<double> make_cam(int model, const double* intr, const double* d
   return c;
 }
 // Host-side dispatch from a run-time value to a template argument, written once: f(std::integral_constant<int, MODEL_X>{}) for the
-// model (`unknown` for an id that is none of the six), f(std::true_type{}) / f(std::false_type{}) for a flag.  f is a generic
-// lambda; its parameter converts to the template argument at compile time: k_project<M, double>, if constexpr (MULTI).
+// model (`unknown` for an id that is none of the six).  f is a generic lambda; its parameter converts to the template argument at
+// compile time: k_project<M, double>.  (with_bool for a flag, with_int for other values: nid_host.hpp.)
 template <typename R, typename F>
 inline R with_model(int model, R unknown, F&& f) {
   switch (model) {
@@ -187,10 +187,6 @@ inline R with_model(int model, R unknown, F&& f) {
     case MODEL_RATIONAL: return f(std::integral_constant<int, MODEL_RATIONAL>{});
     default: return unknown;
   }
-}
-template <typename F>
-inline auto with_bool(bool b, F&& f) {
-  return b ? f(std::true_type{}) : f(std::false_type{});
 }
 
 // ------------------------------------------------------------------------------------------

@@ -2,16 +2,10 @@
 // unit is built with -ffp-contract=off (csrc/Makefile): the fusions wanted are explicit fma calls, and the NEAREST path's
 // +,-,*,/,sqrt match the CPU bit for bit.
 #pragma once
-#include <string>
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include <mutex>
-#include <utility>
-#include <vector>
 
+#include "nid_host.hpp"
 #include "nid_multi.hpp"
-#include "../../include/nidreg.h"
 
 namespace nidreg {
 
@@ -113,70 +107,12 @@ struct VoxCloud2;
 int integrator_stage_cloud2(nidreg_integrator* h, const char* who, const void* data, int64_t num_points, int32_t point_step, int32_t x_offset, int32_t y_offset, int32_t z_offset,
                             int32_t xyz_datatype, int32_t intensity_offset, int32_t intensity_datatype, VoxCloud2* cloud, double4** d_pts, double** d_int);
 int integrator_insert_staged(nidreg_integrator* h, const char* who, int64_t num_points, int64_t* num_skipped);
-
-// error text of the calling thread (nidreg_last_error); returns `code`
-int fail(int code, const std::string& msg);
-
-#define HIP_TRY(expr)                                                                                   \
-  do {                                                                                                  \
-    hipError_t _e = (expr);                                                                             \
-    if (_e != hipSuccess) return fail(NIDREG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-// (internal to libnidreg.so: these helpers add nothing to its dynamic symbol table)
-#define NIDREG_HIDDEN __attribute__((visibility("hidden")))
-
-// Move-only owner of ONE device allocation (hipMalloc, or fine-grained hipExtMallocWithFlags: the shard histogram replicas and
-// exchange blocks; hipFree releases both).  The destructor frees and ignores the error; reset() reports it.  Whoever destroys an
-// owner makes sure first that no kernel still uses the memory (free_handle says how a handle does).
-class NIDREG_HIDDEN DeviceBuf {
- public:
-  DeviceBuf() = default;
-  DeviceBuf(DeviceBuf&& o) noexcept : p_(o.release()) {}
-  DeviceBuf& operator=(DeviceBuf&& o) noexcept {  // (frees what it held AFTER `o` was allocated: a table regrow keeps the old one on failure)
-    if (this != &o) adopt(o.release());
-    return *this;
-  }
-  DeviceBuf(const DeviceBuf&) = delete;
-  DeviceBuf& operator=(const DeviceBuf&) = delete;
-  ~DeviceBuf() { (void)reset(); }
-  hipError_t alloc(size_t bytes) { return (void)reset(), hipMalloc(&p_, bytes); }
-  hipError_t alloc_finegrained(size_t bytes) { return (void)reset(), hipExtMallocWithFlags(&p_, bytes, hipDeviceMallocFinegrained); }
-  void adopt(void* p) { (void)reset(), p_ = p; }  // a hipMalloc'ed pointer handed over as "caller owns"
-  void* release() { return std::exchange(p_, nullptr); }
-  hipError_t reset() { return p_ ? hipFree(release()) : hipSuccess; }
-  template <typename T = void> T* as() const { return static_cast<T*>(p_); }
-  explicit operator bool() const { return p_ != nullptr; }
- private:
-  void* p_ = nullptr;
-};
-// ... and of one host-mapped block that does not come from the per-device pool (nidreg_internal.hpp ResourcePool)
-class NIDREG_HIDDEN HostBuf {
- public:
-  HostBuf() = default;
-  HostBuf(const HostBuf&) = delete;
-  HostBuf& operator=(const HostBuf&) = delete;
-  ~HostBuf() { reset(); }
-  hipError_t alloc(size_t bytes, unsigned flags) { return reset(), hipHostMalloc(&p_, bytes, flags); }
-  void reset() {
-    if (p_) (void)hipHostFree(std::exchange(p_, nullptr));
-  }
-  template <typename T = void> T* as() const { return static_cast<T*>(p_); }
- private:
-  void* p_ = nullptr;
-};
-
-// entry points that take a device id: count -> range -> hipSetDevice, with the caller's name `who` in the error text
-NIDREG_HIDDEN inline int count_devices(const char* who, int* ndev, const char* note = "") {
-  if (hipGetDeviceCount(ndev) != hipSuccess || *ndev <= 0) return fail(NIDREG_ERR_NO_DEVICE, std::string(who) + ": no HIP device" + note);
-  return NIDREG_OK;
-}
-NIDREG_HIDDEN inline int use_device(const char* who, int device_id, const char* note = "") {
-  int ndev = 0;
-  if (const int rc = count_devices(who, &ndev, note)) return rc;
-  if (device_id < 0 || device_id >= ndev) return fail(NIDREG_ERR_INVALID, std::string(who) + ": device_id out of range");
-  HIP_TRY(hipSetDevice(device_id));
-  return NIDREG_OK;
+// the grid of the integrator's grid-strided kernels over n items, and a validated sensor_msgs/PointField datatype as a template
+// argument (kPcUint8 = 2, kPcUint16 = 4, kPcUint32 = 6, kPcFloat32 = 7, kPcFloat64 = 8: nid_voxel_kernels.hpp)
+NIDREG_HIDDEN unsigned vox_grid(int64_t n);
+template <typename F>
+NIDREG_HIDDEN inline bool with_field_type(int32_t t, F&& f) {
+  return with_int<2, 4, 6, 7, 8>(t, f);
 }
 
 // view-culling parameters for the device-side record build (all host values; T = rows of the 4x4)

@@ -2,7 +2,7 @@
 // side by side, on the device (kernels: nid_draw_kernels.hpp).  Stateless, like nidreg_generate_lidar_image: upload, three
 // operations on the null stream (owner words zeroed, k_draw_prims, k_draw_compose), copy back.
 #include "nid_draw_kernels.hpp"
-#include "nid_launch.hpp"
+#include "nid_host.hpp"
 
 using namespace nidreg;
 
@@ -47,12 +47,10 @@ int nidreg_draw(int device_id, const uint8_t* left_gray, int left_w, int left_h,
     const size_t bytes = size_t(num_prims) * kDrawWords * sizeof(int32_t);
     HIP_TRY(d_prims.alloc(bytes));
     HIP_TRY(hipMemcpy(d_prims.as<void>(), prims, bytes, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_draw_prims, dim3(unsigned(num_prims)), dim3(kDrawWave), 0, nullptr, d_prims.as<int32_t>(), cw, left_h, d_owner.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(k_draw_prims, unsigned(num_prims), kDrawWave, 0, nullptr, d_prims.as<int32_t>(), cw, left_h, d_owner.as<uint32_t>()));
   }
-  hipLaunchKernelGGL(k_draw_compose, dim3(unsigned((npix + kDrawThreads - 1) / kDrawThreads)), dim3(kDrawThreads), 0, nullptr, d_left.as<uint8_t>(), left_w, left_h, d_right.as<uint8_t>(),
-                     right_w, right_h, cw, d_owner.as<uint32_t>(), d_prims.as<int32_t>(), d_out.as<uint8_t>());
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch(k_draw_compose, blocks_for(npix, kDrawThreads), kDrawThreads, 0, nullptr, d_left.as<uint8_t>(), left_w, left_h, d_right.as<uint8_t>(), right_w, right_h, cw,
+                 d_owner.as<uint32_t>(), d_prims.as<int32_t>(), d_out.as<uint8_t>()));
   HIP_TRY(hipMemcpy(out_rgb, d_out.as<void>(), npix * 3, hipMemcpyDeviceToHost));  // (synchronises the null stream)
   return NIDREG_OK;
 }

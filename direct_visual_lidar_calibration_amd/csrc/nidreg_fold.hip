@@ -40,12 +40,8 @@ int nidreg_cloud_fold_ids(const nidreg_cloud* cloud, uint64_t seed, double cell,
   int* const d_count = static_cast<int*>(arena.carve(b_count));
   long long* const d_sizes = static_cast<long long*>(arena.carve(b_sizes));
   if (!d_ids || !d_count || !d_sizes) return fail(NIDREG_ERR_HIP, std::string(who) + ": scratch arena exhausted");
-  hipLaunchKernelGGL(k_fold_ids, dim3(unsigned(nblocks)), dim3(kFoldThreads), 0, nullptr, cloud->d_pts.as<double>(), (long long)n, seed, cell, num_folds, d_ids, d_count);
-  HIP_TRY(hipGetLastError());
-  if (sizes_out) {
-    hipLaunchKernelGGL(k_fold_sizes, dim3(unsigned((num_folds + kFoldThreads - 1) / kFoldThreads)), dim3(kFoldThreads), 0, nullptr, d_count, nblocks, num_folds, d_sizes);
-    HIP_TRY(hipGetLastError());
-  }
+  HIP_TRY(launch(k_fold_ids, unsigned(nblocks), kFoldThreads, 0, nullptr, cloud->d_pts.as<double>(), n, seed, cell, num_folds, d_ids, d_count));
+  if (sizes_out) HIP_TRY(launch(k_fold_sizes, blocks_for(num_folds, kFoldThreads), kFoldThreads, 0, nullptr, d_count, nblocks, num_folds, d_sizes));
   HIP_TRY(hipMemcpy(folds_out, d_ids, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost));  // (synchronises the null stream)
   if (sizes_out) {
     static_assert(sizeof(long long) == sizeof(int64_t), "k_fold_sizes writes the caller's int64_t");
@@ -81,9 +77,7 @@ int nidreg_cloud_fold(const nidreg_cloud* cloud, uint64_t seed, double cell, int
     int* const d_offset = static_cast<int*>(arena.carve(b_offset));
     int32_t* const d_idx = indices_out ? static_cast<int32_t*>(arena.carve(b_idx)) : nullptr;
     if (!d_flag || !d_count || !d_offset || (indices_out && !d_idx)) return fail(NIDREG_ERR_HIP, std::string(who) + ": scratch arena exhausted");
-    hipLaunchKernelGGL(k_fold_flags, dim3(unsigned(ntiles)), dim3(kFoldThreads), 0, nullptr, cloud->d_pts.as<double>(), (long long)n, seed, cell, num_folds, fold, complement ? 1 : 0,
-                       d_flag, d_count);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(k_fold_flags, unsigned(ntiles), kFoldThreads, 0, nullptr, cloud->d_pts.as<double>(), n, seed, cell, num_folds, fold, complement ? 1 : 0, d_flag, d_count));
     HIP_TRY(launch_select_scan(d_count, ntiles, d_offset));
     HIP_TRY(hipMemcpy(&total, d_offset + ntiles, sizeof(int), hipMemcpyDeviceToHost));  // (synchronises the null stream)
     if (total < 0 || int64_t(total) > n) return fail(NIDREG_ERR_HIP, std::string(who) + ": the scan counted " + std::to_string(total) + " of " + std::to_string(n) + " points");

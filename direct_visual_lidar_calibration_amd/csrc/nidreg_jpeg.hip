@@ -3,18 +3,13 @@
 // then upload of the quantised coefficients and tables, the launches, the copy back.  No CPU path for the arithmetic.
 #include "nid_jpeg_host.hpp"
 #include "nid_jpeg_kernels.hpp"
-#include "nid_launch.hpp"
-
-#include <chrono>
-#include <cstring>
-#include <new>
-#include <string>
+#include "nid_host.hpp"
 
 using namespace nidreg;
 
 namespace {
 
-thread_local double g_jpeg_ms[4] = {0, 0, 0, 0};  // of this thread's last nidreg_jpeg_decode_gray: entropy, upload, kernels, copy back
+thread_local PhaseClock<4> g_jpeg_clock;  // of this thread's last nidreg_jpeg_decode_gray: entropy, upload, kernels, copy back
 
 int refuse(const char* who, const std::string& reason) {
   return fail(NIDREG_ERR_INVALID, std::string(who) + ": JPEG images are not decoded here unless they are baseline 8-bit Huffman streams (" + reason + ")");
@@ -31,8 +26,6 @@ int parse_stream(const char* who, const uint8_t* data, int64_t size, bool entrop
   }
   return NIDREG_OK;
 }
-
-double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 
 size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -71,12 +64,12 @@ int nidreg_jpeg_decode_gray(int device_id, const uint8_t* data, int64_t size, in
   if (!out) return fail(NIDREG_ERR_INVALID, std::string(who) + ": null out");
   if (mode != NIDREG_JPEG_GRAY_LUMA && mode != NIDREG_JPEG_GRAY_BGR) return fail(NIDREG_ERR_INVALID, std::string(who) + ": unknown mode");
   if (row_stride < 0) return fail(NIDREG_ERR_INVALID, std::string(who) + ": negative row_stride");
-  const auto t_entropy = std::chrono::steady_clock::now();
+  g_jpeg_clock.start();
   nidjpeg::Stream s;
   if (const int rc = parse_stream(who, data, size, true, s)) return rc;
   const int64_t stride = row_stride > 0 ? row_stride : int64_t(s.width);
   if (stride < s.width) return fail(NIDREG_ERR_INVALID, std::string(who) + ": row_stride below the width");
-  g_jpeg_ms[0] = ms_since(t_entropy);
+  g_jpeg_clock.lap(0);
   if (const int rc = use_device(who, device_id)) return rc;
 
   // the planes the colour kernel needs: none for one component or the LUMA mode (the Y blocks go straight into the cropped image)
@@ -88,7 +81,7 @@ int nidreg_jpeg_decode_gray(int device_id, const uint8_t* data, int64_t size, in
   for (int c = 0; c < ncomp_used; c++) used_blocks += size_t(s.comp[c].bw) * size_t(s.comp[c].bh);
 
   // one upload block: the used components' coefficients (they come first in s.coef), then their tables, 64 entries each
-  const auto t_upload = std::chrono::steady_clock::now();
+  g_jpeg_clock.start();  // (use_device belongs to no phase)
   const size_t coef_bytes = used_blocks * 64 * sizeof(int16_t);
   DeviceBuf d_in, d_planes, d_out;
   HIP_TRY(d_in.alloc(coef_bytes + 3 * 64 * sizeof(uint16_t)));
@@ -105,19 +98,17 @@ int nidreg_jpeg_decode_gray(int device_id, const uint8_t* data, int64_t size, in
   for (int c = 0; c < 3; c++) std::memcpy(tables[c], s.qt[s.comp[c < s.ncomp ? c : 0].tq], sizeof(tables[c]));
   HIP_TRY(hipMemcpy(d_in.as<void>(), s.coef.data(), coef_bytes, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_in.as<uint8_t>() + coef_bytes, tables, sizeof(tables), hipMemcpyHostToDevice));
-  g_jpeg_ms[1] = ms_since(t_upload);
+  g_jpeg_clock.lap(1);
 
-  const auto t_kernels = std::chrono::steady_clock::now();
   const uint16_t* const d_qt = reinterpret_cast<const uint16_t*>(d_in.as<uint8_t>() + coef_bytes);
   for (int c = 0; c < ncomp_used; c++) {
     const nidjpeg::Component& k = s.comp[c];
     const long long nblocks = (long long)k.bw * k.bh;
-    const unsigned grid = unsigned((nblocks + kJpegBlocksPerGroup - 1) / kJpegBlocksPerGroup);
     uint8_t* const dst = color ? d_planes.as<uint8_t>() + plane_off[c] : d_out.as<uint8_t>();
     const long long dst_stride = color ? (long long)k.bw * 8 : (long long)out_stride;
     const int dst_rows = color ? k.bh * 8 : s.height;
-    hipLaunchKernelGGL(k_jpeg_idct, dim3(grid), dim3(kJpegIdctThreads), 0, nullptr, d_in.as<int16_t>() + k.block_offset * 64, d_qt + 64 * c, nblocks, k.bw, dst, dst_stride, dst_rows);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(k_jpeg_idct, blocks_for(nblocks, kJpegBlocksPerGroup), kJpegIdctThreads, 0, nullptr, d_in.as<int16_t>() + k.block_offset * 64, d_qt + 64 * c, nblocks, k.bw, dst, dst_stride,
+                   dst_rows));
   }
   if (color) {
     JpegChroma g;
@@ -128,24 +119,17 @@ int nidreg_jpeg_decode_gray(int device_id, const uint8_t* data, int64_t size, in
     g.hs = s.hmax, g.vs = s.vmax;
     g.fancy = s.hmax == 2 && s.comp[1].dw > 2;
     const int w4 = int(out_stride / 4);
-    const long long groups = (long long)w4 * s.height;
-    hipLaunchKernelGGL(k_jpeg_gray_bgr, dim3(unsigned((groups + kJpegColorThreads - 1) / kJpegColorThreads)), dim3(kJpegColorThreads), 0, nullptr, d_planes.as<uint8_t>() + plane_off[0],
-                       (long long)s.comp[0].bw * 8, g, w4, s.height, d_out.as<uint8_t>(), (long long)out_stride);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(k_jpeg_gray_bgr, blocks_for((long long)w4 * s.height, kJpegColorThreads), kJpegColorThreads, 0, nullptr, d_planes.as<uint8_t>() + plane_off[0],
+                   (long long)s.comp[0].bw * 8, g, w4, s.height, d_out.as<uint8_t>(), out_stride));
   }
   HIP_TRY(hipStreamSynchronize(nullptr));
-  g_jpeg_ms[2] = ms_since(t_kernels);
+  g_jpeg_clock.lap(2);
 
-  const auto t_copy = std::chrono::steady_clock::now();
   HIP_TRY(hipMemcpy2D(out, size_t(stride), d_out.as<void>(), out_stride, W, H, hipMemcpyDeviceToHost));  // W bytes a row: the caller's padding stays
-  g_jpeg_ms[3] = ms_since(t_copy);
+  g_jpeg_clock.lap(3);
   return NIDREG_OK;
 }
 
-int nidreg_jpeg_get_timing(double* ms4) {
-  if (!ms4) return fail(NIDREG_ERR_INVALID, "nidreg_jpeg_get_timing: null argument");
-  std::memcpy(ms4, g_jpeg_ms, sizeof(g_jpeg_ms));
-  return NIDREG_OK;
-}
+int nidreg_jpeg_get_timing(double* ms4) { return g_jpeg_clock.read("nidreg_jpeg_get_timing", ms4); }
 
 }  // extern "C"

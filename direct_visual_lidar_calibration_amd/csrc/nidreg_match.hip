@@ -2,7 +2,7 @@
 // over a 6/5 pyramid and mutual-best Hamming matching on the device (kernels: nid_match_kernels.hpp).  A classical stand-in for the
 // reference's scripts/find_matches_superglue.py, of which only the command line and the JSON keys are kept (find_matches.py).
 #include "nid_match_kernels.hpp"
-#include "nid_launch.hpp"
+#include "nid_host.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -14,7 +14,7 @@ using namespace nidreg;
 
 namespace {
 
-dim3 tiles(int w, int h) { return dim3(unsigned((w + kFeatTileW - 1) / kFeatTileW), unsigned((h + kFeatTileH - 1) / kFeatTileH)); }
+dim3 tiles(int w, int h) { return dim3(blocks_for(w, kFeatTileW), blocks_for(h, kFeatTileH)); }
 
 }  // namespace
 
@@ -75,8 +75,7 @@ int nidreg_features_detect(int device_id, const uint8_t* image, int width, int h
       uint8_t *img_a = pyr, *msk_a = f, *img_b = f + n0, *msk_b = f + 2 * n0;
       HIP_TRY(hipMemcpyAsync(msk_a, d_mask.as<void>(), n0, hipMemcpyDeviceToDevice, nullptr));
       for (int p = 0; p < fill_passes; p++) {
-        hipLaunchKernelGGL(k_fill_pass, tiles(width, height), dim3(kFeatThreads), 0, nullptr, img_a, msk_a, img_b, msk_b, width, height);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(k_fill_pass, tiles(width, height), kFeatThreads, 0, nullptr, img_a, msk_a, img_b, msk_b, width, height));
         std::swap(img_a, img_b), std::swap(msk_a, msk_b);
       }
       if (img_a != pyr) HIP_TRY(hipMemcpyAsync(pyr, img_a, n0, hipMemcpyDeviceToDevice, nullptr));
@@ -85,18 +84,12 @@ int nidreg_features_detect(int device_id, const uint8_t* image, int width, int h
   for (int l = 0; l < nl; l++) {
     uint8_t* const cur = pyr + off[size_t(l)];
     const int w = lv.w[l], h = lv.h[l];
-    if (l > 0) {
-      hipLaunchKernelGGL(k_pyr_down, tiles(w, h), dim3(kFeatThreads), 0, nullptr, pyr + off[size_t(l - 1)], lv.w[l - 1], lv.h[l - 1], cur, w, h);
-      HIP_TRY(hipGetLastError());
-    }
+    if (l > 0) HIP_TRY(launch(k_pyr_down, tiles(w, h), kFeatThreads, 0, nullptr, pyr + off[size_t(l - 1)], lv.w[l - 1], lv.h[l - 1], cur, w, h));
     lv.smooth[l] = smooth + off[size_t(l)];
-    hipLaunchKernelGGL(k_smooth, tiles(w, h), dim3(kFeatThreads), 0, nullptr, cur, w, h, smooth + off[size_t(l)]);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_fast_score, tiles(w, h), dim3(kFeatThreads), 0, nullptr, cur, w, h, d_score.as<uint8_t>());
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_nms_keys, tiles(w, h), dim3(kFeatThreads), 0, nullptr, d_score.as<uint8_t>(), w, h, l, nms_radius, fast_threshold, d_mask.as<uint8_t>(), width, height, lv.num[l],
-                       lv.den[l], d_keys.as<match_u64>() + off[size_t(l)]);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(k_smooth, tiles(w, h), kFeatThreads, 0, nullptr, cur, w, h, smooth + off[size_t(l)]));
+    HIP_TRY(launch(k_fast_score, tiles(w, h), kFeatThreads, 0, nullptr, cur, w, h, d_score.as<uint8_t>()));
+    HIP_TRY(launch(k_nms_keys, tiles(w, h), kFeatThreads, 0, nullptr, d_score.as<uint8_t>(), w, h, l, nms_radius, fast_threshold, d_mask.as<uint8_t>(), width, height, lv.num[l], lv.den[l],
+                   d_keys.as<match_u64>() + off[size_t(l)]));
   }
   // the order of the keypoints is the order of their keys (48 significant bits; kFeatNoKey's low 48 bits are all ones: last)
   size_t tmp_bytes = 0;
@@ -104,16 +97,14 @@ int nidreg_features_detect(int device_id, const uint8_t* image, int width, int h
   HIP_TRY(d_tmp.alloc(std::max<size_t>(tmp_bytes, 16)));
   HIP_TRY(rocprim::radix_sort_keys(d_tmp.as<void>(), tmp_bytes, d_keys.as<match_u64>(), d_keys2.as<match_u64>(), nt, 0, 48, hipStream_t(nullptr)));
   HIP_TRY(hipMemsetAsync(d_count.as<void>(), 0, sizeof(int), nullptr));
-  hipLaunchKernelGGL(k_count_keys, dim3(unsigned((total + kFeatThreads - 1) / kFeatThreads)), dim3(kFeatThreads), 0, nullptr, d_keys2.as<match_u64>(), int(total), d_count.as<int>());
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch(k_count_keys, blocks_for(total, kFeatThreads), kFeatThreads, 0, nullptr, d_keys2.as<match_u64>(), int(total), d_count.as<int>()));
   int found = 0;
   HIP_TRY(hipMemcpy(&found, d_count.as<void>(), sizeof(int), hipMemcpyDeviceToHost));  // (synchronises the null stream)
   const int n = std::min(found, cap);
   if (n > 0) {
     HIP_TRY(d_kpts.alloc(size_t(n) * 4 * sizeof(int32_t)));
     HIP_TRY(d_desc.alloc(size_t(n) * 8 * sizeof(uint32_t)));
-    hipLaunchKernelGGL(k_describe, dim3(unsigned(n)), dim3(kBriefPairs), 0, nullptr, d_keys2.as<match_u64>(), lv, d_kpts.as<int32_t>(), d_desc.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(k_describe, unsigned(n), kBriefPairs, 0, nullptr, d_keys2.as<match_u64>(), lv, d_kpts.as<int32_t>(), d_desc.as<uint32_t>()));
     HIP_TRY(hipMemcpy(kpts_out, d_kpts.as<void>(), size_t(n) * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(desc_out, d_desc.as<void>(), size_t(n) * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost));
   }
@@ -146,13 +137,9 @@ int nidreg_features_match(int device_id, const uint32_t* desc0, int n0, const ui
   HIP_TRY(hipMemcpy(d1, desc1, s1 * 32, hipMemcpyHostToDevice));
   int32_t* const r = d_res.as<int32_t>();
   int32_t *best01 = r, *dist01 = r + s0, *sec01 = r + 2 * s0, *match = r + 3 * s0, *best10 = r + 4 * s0, *dist10 = best10 + s1, *sec10 = best10 + 2 * s1;
-  hipLaunchKernelGGL(k_hamming_best, dim3(unsigned((n0 + kMatchThreads - 1) / kMatchThreads)), dim3(kMatchThreads), 0, nullptr, d0, n0, d1, n1, best01, dist01, sec01);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_hamming_best, dim3(unsigned((n1 + kMatchThreads - 1) / kMatchThreads)), dim3(kMatchThreads), 0, nullptr, d1, n1, d0, n0, best10, dist10, sec10);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_mutual, dim3(unsigned((n0 + kFeatThreads - 1) / kFeatThreads)), dim3(kFeatThreads), 0, nullptr, n0, best01, dist01, sec01, best10, max_distance, (long long)ratio_num,
-                     (long long)ratio_den, match);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch(k_hamming_best, blocks_for(n0, kMatchThreads), kMatchThreads, 0, nullptr, d0, n0, d1, n1, best01, dist01, sec01));
+  HIP_TRY(launch(k_hamming_best, blocks_for(n1, kMatchThreads), kMatchThreads, 0, nullptr, d1, n1, d0, n0, best10, dist10, sec10));
+  HIP_TRY(launch(k_mutual, blocks_for(n0, kFeatThreads), kFeatThreads, 0, nullptr, n0, best01, dist01, sec01, best10, max_distance, ratio_num, ratio_den, match));
   std::vector<int32_t> out(4 * s0);
   HIP_TRY(hipMemcpy(out.data(), r, 4 * s0 * sizeof(int32_t), hipMemcpyDeviceToHost));  // (synchronises the null stream)
   std::memcpy(dist_out, out.data() + s0, s0 * sizeof(int32_t));

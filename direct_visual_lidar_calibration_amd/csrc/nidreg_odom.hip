@@ -85,11 +85,9 @@ int covariances(const char* who, nidreg_odom* h, const double* points, int32_t m
   if (neighbors_in) {
     HIP_TRY(hipMemcpy(d_nbr.as<void>(), neighbors_in, nk * sizeof(int), hipMemcpyHostToDevice));
   } else {
-    hipLaunchKernelGGL(k_odom_knn, dim3(waves_of(m)), dim3(kOdomWave), 0, nullptr, d_pts.as<const double>(), int(m), int(k), d_nbr.as<int>());
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(k_odom_knn, waves_of(m), kOdomWave, 0, nullptr, d_pts.as<const double>(), m, k, d_nbr.as<int>()));
   }
-  hipLaunchKernelGGL(k_odom_cov, dim3(waves_of(m)), dim3(kOdomWave), 0, nullptr, d_pts.as<const double>(), d_nbr.as<const int>(), int(m), int(k), d_normals.as<double>(), d_covs.as<double>());
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch(k_odom_cov, waves_of(m), kOdomWave, 0, nullptr, d_pts.as<const double>(), d_nbr.as<const int>(), m, k, d_normals.as<double>(), d_covs.as<double>()));
   if (neighbors_out) HIP_TRY(hipMemcpy(neighbors_out, d_nbr.as<void>(), nk * sizeof(int), hipMemcpyDeviceToHost));
   if (normals) HIP_TRY(hipMemcpy(normals, d_normals.as<void>(), size_t(m) * 24, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(covs, d_covs.as<void>(), size_t(m) * 48, hipMemcpyDeviceToHost));
@@ -113,27 +111,15 @@ int upload_poses(nidreg_odom* h, const char* who, const double* poses, int32_t n
   return NIDREG_OK;
 }
 
-template <int XyzType, int IntType>
-void deskew_launch(int32_t time_datatype, const VoxCloud2& c, const OdomDeskew& d, double4* pts, double* inten) {
-  const dim3 grid(unsigned(std::max<int64_t>(1, std::min<int64_t>((c.n + kVoxThreads - 1) / kVoxThreads, kVoxMaxBlocks)))), block(kVoxThreads);
-  switch (time_datatype) {
-    case kPcUint32: hipLaunchKernelGGL((k_odom_deskew<XyzType, IntType, kPcUint32>), grid, block, 0, nullptr, c, d, pts, inten); break;
-    case kPcFloat32: hipLaunchKernelGGL((k_odom_deskew<XyzType, IntType, kPcFloat32>), grid, block, 0, nullptr, c, d, pts, inten); break;
-    case kPcFloat64: hipLaunchKernelGGL((k_odom_deskew<XyzType, IntType, kPcFloat64>), grid, block, 0, nullptr, c, d, pts, inten); break;
-    default: hipLaunchKernelGGL((k_odom_deskew<XyzType, IntType, 0>), grid, block, 0, nullptr, c, d, pts, inten); break;
-  }
-}
-
-// the field types as template arguments (the typed dispatch of nid_device.hpp: a generic lambda receives an integral_constant)
-template <typename F>
-void with_field_type(int32_t t, F&& f) {
-  switch (t) {
-    case kPcUint8: return f(std::integral_constant<int, kPcUint8>{});
-    case kPcUint16: return f(std::integral_constant<int, kPcUint16>{});
-    case kPcUint32: return f(std::integral_constant<int, kPcUint32>{});
-    case kPcFloat32: return f(std::integral_constant<int, kPcFloat32>{});
-    default: return f(std::integral_constant<int, kPcFloat64>{});
-  }
+// the deskew kernel for the record's field types, all validated by the caller (time_datatype 0: no time field)
+hipError_t deskew_launch(int32_t xyz_datatype, int32_t intensity_datatype, int32_t time_datatype, const VoxCloud2& c, const OdomDeskew& d, double4* pts, double* inten) {
+  hipError_t e = hipErrorInvalidValue;
+  with_int<kPcFloat32, kPcFloat64>(xyz_datatype, [&](auto X) {
+    with_field_type(intensity_datatype, [&](auto I) {
+      with_int<kPcUint32, kPcFloat32, kPcFloat64, 0>(time_datatype, [&](auto T) { e = launch(k_odom_deskew<X, I, T>, vox_grid(c.n), kVoxThreads, 0, nullptr, c, d, pts, inten); });
+    });
+  });
+  return e;
 }
 
 }  // namespace
@@ -222,18 +208,16 @@ int nidreg_odom_model_insert(nidreg_odom* h, const double* points, const double*
   HIP_TRY(hipMemcpy(d_order.as<void>(), order.data(), size_t(m) * sizeof(int), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_gbegin.as<void>(), gbegin.data(), size_t(groups + 1) * sizeof(int), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_gkey.as<void>(), gkey.data(), size_t(groups) * sizeof(vox_u64), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_odom_model_insert, dim3(unsigned(groups)), dim3(kOdomWave), 0, nullptr, d_pts.as<const double>(), d_covs.as<const double>(), d_order.as<const int>(),
-                     d_gbegin.as<const int>(), d_gkey.as<const vox_u64>(), groups, h->thresh_sq, h->d_table.as<OdomVoxel>(), unsigned(h->table_cap - 1), h->d_blocks.as<OdomBlock>(),
-                     h->d_next.as<int>(), h->cap_blocks, h->d_counters.as<vox_u64>(), h->d_free.as<const int>(), int(h->lru_count));
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch(k_odom_model_insert, unsigned(groups), kOdomWave, 0, nullptr, d_pts.as<const double>(), d_covs.as<const double>(), d_order.as<const int>(), d_gbegin.as<const int>(),
+                 d_gkey.as<const vox_u64>(), groups, h->thresh_sq, h->d_table.as<OdomVoxel>(), unsigned(h->table_cap - 1), h->d_blocks.as<OdomBlock>(), h->d_next.as<int>(), h->cap_blocks,
+                 h->d_counters.as<vox_u64>(), h->d_free.as<const int>(), h->lru_count));
   // ivox.cpp:169-178: the horizon must be positive, and only every lru_cycle-th insert looks
   const int64_t horizon = int64_t(h->lru_count) - h->lru_thresh;
   const bool evict = h->lru_thresh > 0 && horizon > 0 && h->lru_count % h->lru_cycle == 0;
   if (evict) {
     HIP_TRY(hipMemsetAsync(h->d_spare.as<void>(), 0, size_t(h->table_cap) * sizeof(OdomVoxel), nullptr));
-    hipLaunchKernelGGL(k_odom_evict, dim3(unsigned((h->table_cap + kOdomEvictThreads - 1) / kOdomEvictThreads)), dim3(kOdomEvictThreads), 0, nullptr, h->d_table.as<const OdomVoxel>(),
-                       h->d_spare.as<OdomVoxel>(), unsigned(h->table_cap - 1), h->d_next.as<const int>(), h->cap_blocks, h->d_free.as<int>(), h->d_counters.as<vox_u64>(), int(horizon));
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(k_odom_evict, blocks_for(h->table_cap, kOdomEvictThreads), kOdomEvictThreads, 0, nullptr, h->d_table.as<const OdomVoxel>(), h->d_spare.as<OdomVoxel>(),
+                   unsigned(h->table_cap - 1), h->d_next.as<const int>(), h->cap_blocks, h->d_free.as<int>(), h->d_counters.as<vox_u64>(), int(horizon)));
   }
   vox_u64 cnt[kCounters];
   HIP_TRY(hipMemcpy(cnt, h->d_counters.as<void>(), sizeof(cnt), hipMemcpyDeviceToHost));
@@ -353,14 +337,12 @@ int nidreg_odom_linearize(nidreg_odom* h, const double* poses, int32_t num_poses
   h->linearized = true;
   if (h->m == 0) return NIDREG_OK;
   const unsigned waves = waves_of(h->m);
-  with_bool(h->lru_thresh > 0, [&](auto Touch) {  // with the eviction on, the search stamps the voxels it finds; off, it stores nothing
-    hipLaunchKernelGGL((k_odom_linearize<decltype(Touch)::value>), dim3(waves), dim3(kOdomWave), 0, nullptr, h->d_pts.as<const double>(), h->d_covs.as<const double>(), h->d_tidx.as<const int>(),
-                       h->m, h->d_poses.as<const double>(), model_of(h), max_correspondence_dist_sq, h->d_found.as<int>(), h->d_target.as<double>(), h->d_mahal.as<double>(),
-                       h->d_partials.as<double>(), int(h->lru_count));
-  });
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_odom_sum, dim3(1), dim3(128), 0, nullptr, h->d_partials.as<const double>(), int(waves), kOdomSums, h->d_out.as<double>());
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(with_bool(h->lru_thresh > 0, [&](auto Touch) {  // with the eviction on, the search stamps the voxels it finds; off, it stores nothing
+    return launch(k_odom_linearize<Touch>, waves, kOdomWave, 0, nullptr, h->d_pts.as<const double>(), h->d_covs.as<const double>(), h->d_tidx.as<const int>(), h->m,
+                  h->d_poses.as<const double>(), model_of(h), max_correspondence_dist_sq, h->d_found.as<int>(), h->d_target.as<double>(), h->d_mahal.as<double>(), h->d_partials.as<double>(),
+                  h->lru_count);
+  }));
+  HIP_TRY(launch(k_odom_sum, 1, 128, 0, nullptr, h->d_partials.as<const double>(), int(waves), kOdomSums, h->d_out.as<double>()));
   HIP_TRY(hipMemcpy(out122, h->d_out.as<void>(), kOdomSums * 8, hipMemcpyDeviceToHost));
   return NIDREG_OK;
 }
@@ -373,11 +355,9 @@ int nidreg_odom_error(nidreg_odom* h, const double* poses12, int32_t num_poses, 
   out2[0] = out2[1] = 0.0;
   if (h->m == 0) return NIDREG_OK;
   const unsigned waves = waves_of(h->m);
-  hipLaunchKernelGGL(k_odom_error, dim3(waves), dim3(kOdomWave), 0, nullptr, h->d_pts.as<const double>(), h->d_tidx.as<const int>(), h->m, h->d_poses.as<const double>(), h->d_found.as<const int>(),
-                     h->d_target.as<const double>(), h->d_mahal.as<const double>(), h->d_partials.as<double>());
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_odom_sum, dim3(1), dim3(128), 0, nullptr, h->d_partials.as<const double>(), int(waves), 2, h->d_out.as<double>());
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch(k_odom_error, waves, kOdomWave, 0, nullptr, h->d_pts.as<const double>(), h->d_tidx.as<const int>(), h->m, h->d_poses.as<const double>(), h->d_found.as<const int>(),
+                 h->d_target.as<const double>(), h->d_mahal.as<const double>(), h->d_partials.as<double>()));
+  HIP_TRY(launch(k_odom_sum, 1, 128, 0, nullptr, h->d_partials.as<const double>(), int(waves), 2, h->d_out.as<double>()));
   HIP_TRY(hipMemcpy(out2, h->d_out.as<void>(), 16, hipMemcpyDeviceToHost));
   return NIDREG_OK;
 }
@@ -421,10 +401,7 @@ int nidreg_odom_deskew_insert(nidreg_integrator* integrator, const void* data, i
   for (int i = 0; i < 9; i++) d.R0[i] = begin12[i];
   for (int i = 0; i < 3; i++) d.t0[i] = begin12[9 + i], d.w[i] = rotvec3[i], d.dt[i] = dtrans3[i];
   d.scale = time_scale, d.shift = time_shift, d.max_time = max_time, d.ot = time_offset;
-  with_bool(xyz_datatype == kPcFloat32, [&](auto F32) {
-    with_field_type(intensity_datatype, [&](auto I) { deskew_launch<(decltype(F32)::value ? int(kPcFloat32) : int(kPcFloat64)), decltype(I)::value>(time_datatype, c, d, d_pts, d_int); });
-  });
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(deskew_launch(xyz_datatype, intensity_datatype, time_datatype, c, d, d_pts, d_int));
   return integrator_insert_staged(integrator, who, num_points, num_skipped);
 }
 

@@ -3,15 +3,10 @@
 // BEFORE the device is touched), ONE upload of column table + beam table + transform + the packets as the batcher laid them out, one
 // launch (two with returns_per_packet), the copy back.  Nothing stays on a device between calls: the tables are the caller's, built
 // from the sensor's metadata.  No CPU path for the arithmetic.
-#include "nid_launch.hpp"
+#include "nid_host.hpp"
 #include "nid_ouster_kernels.hpp"
 
-#include <chrono>
 #include <cmath>
-#include <cstring>
-#include <new>
-#include <string>
-#include <vector>
 
 using namespace nidreg;
 
@@ -21,9 +16,7 @@ constexpr int64_t kMaxPackets = 4096;   // two turns of 2048 columns at one colu
 constexpr int64_t kMaxStride = 32768;   // the largest packet (LEGACY, H = 128, C = 16) is 24896 bytes
 constexpr int kPoseDoubles = 16;        // transform12, n, padding: keeps the packet area 8-byte aligned
 
-thread_local double g_ouster_ms[3] = {0, 0, 0};  // of this thread's last nidreg_ouster_decode: upload, kernel, copy back
-
-double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+thread_local PhaseClock<3> g_ouster_clock;  // of this thread's last nidreg_ouster_decode: upload, kernel, copy back
 
 }  // namespace
 
@@ -39,9 +32,7 @@ int nidreg_ouster_decode(int device_id, const uint8_t* packets, int64_t num_pack
   if (W < 16 || W > 4096) return fail(NIDREG_ERR_INVALID, who + ": W " + std::to_string(W) + " outside [16, 4096]");
   if (C < 1 || C > 16) return fail(NIDREG_ERR_INVALID, who + ": C " + std::to_string(C) + " outside [1, 16]");
   const int64_t size = ouster_packet_bytes(profile, H, C);
-  if (packet_stride < size) return fail(NIDREG_ERR_INVALID, who + ": packet_stride " + std::to_string(packet_stride) + " is below the " + std::to_string(size) + " bytes of a packet");
-  if (packet_stride > kMaxStride) return fail(NIDREG_ERR_INVALID, who + ": packet_stride " + std::to_string(packet_stride) + " is above " + std::to_string(kMaxStride));
-  if (num_packets < 0 || num_packets > kMaxPackets) return fail(NIDREG_ERR_INVALID, who + ": num_packets " + std::to_string(num_packets) + " outside [0, " + std::to_string(kMaxPackets) + "]");
+  if (const int rc = check_packets(who, num_packets, kMaxPackets, packet_stride, size, kMaxStride)) return rc;
   if (num_packets > 0 && (!packets || !column_table || !beam_table || !transform12 || !records_out))
     return fail(NIDREG_ERR_INVALID, who + ": null packets, column_table, beam_table, transform12 or records_out");
   for (int i = 0; column_table && i < 2 * W; i++)
@@ -54,69 +45,44 @@ int nidreg_ouster_decode(int device_id, const uint8_t* packets, int64_t num_pack
   if (num_packets == 0) return NIDREG_OK;
   if (const int rc = use_device(who.c_str(), device_id)) return rc;
 
-  const auto t_upload = std::chrono::steady_clock::now();
-  // one staging block, one copy: [column table: W x 2][beam table: H x 4][transform12, n, 0, 0, 0][the packet area, then padding to whole dwords]
+  g_ouster_clock.start();
+  // one staging block, one copy: [column table: W x 2][beam table: H x 4][transform12, n, 0, 0, 0][the packet area]
   const size_t N = size_t(num_packets);
-  const size_t column_bytes = size_t(W) * 2 * sizeof(double), beam_bytes = size_t(H) * 4 * sizeof(double), pose_bytes = kPoseDoubles * sizeof(double);
-  const size_t packet_bytes = (N - 1) * size_t(packet_stride) + size_t(size);  // the last packet's tail is not the caller's to give
-  const size_t total = column_bytes + beam_bytes + pose_bytes + ((packet_bytes + 3) / 4) * 4 + 4;
-  std::vector<uint8_t> stage;
-  try {
-    stage.assign(total, 0);
-  } catch (const std::bad_alloc&) {  // (nothing may leave an extern "C" function)
-    return fail(NIDREG_ERR_INVALID, who + ": no host memory for a staging block of " + std::to_string(total) + " bytes");
-  }
-  std::memcpy(stage.data(), column_table, column_bytes);
-  std::memcpy(stage.data() + column_bytes, beam_table, beam_bytes);
-  std::memcpy(stage.data() + column_bytes + beam_bytes, transform12, 12 * sizeof(double));
-  std::memcpy(stage.data() + column_bytes + beam_bytes + 12 * sizeof(double), &n_mm, sizeof(double));
-  std::memcpy(stage.data() + column_bytes + beam_bytes + pose_bytes, packets, packet_bytes);
+  const size_t column_bytes = size_t(W) * 2 * sizeof(double), beam_bytes = size_t(H) * 4 * sizeof(double), packet_bytes = packet_area_bytes(num_packets, packet_stride, size);
+  StagingBlock stage;
+  const size_t o_columns = stage.part(column_bytes), o_beams = stage.part(beam_bytes), o_pose = stage.part(kPoseDoubles * sizeof(double)), o_packets = stage.packet_part(packet_bytes);
+  if (const int rc = stage.take(who)) return rc;
+  stage.put(o_columns, column_table, column_bytes);
+  stage.put(o_beams, beam_table, beam_bytes);
+  stage.put(o_pose, transform12, 12 * sizeof(double));
+  stage.put(o_pose + 12 * sizeof(double), &n_mm, sizeof(double));
+  stage.put(o_packets, packets, packet_bytes);
   const size_t record_words = N * size_t(C) * size_t(H) * kOusterRecordWords;
-  DeviceBuf d_in, d_rec, d_col, d_ret;
-  HIP_TRY(d_in.alloc(total));
+  DeviceBuf d_rec, d_col, d_ret;
+  HIP_TRY(stage.upload());
   HIP_TRY(d_rec.alloc(record_words * sizeof(uint32_t)));
   if (returns_per_packet) {
     HIP_TRY(d_col.alloc(N * size_t(C) * sizeof(int32_t)));
     HIP_TRY(d_ret.alloc(N * sizeof(int32_t)));
   }
-  HIP_TRY(hipMemcpy(d_in.as<void>(), stage.data(), total, hipMemcpyHostToDevice));
-  g_ouster_ms[0] = ms_since(t_upload);
+  g_ouster_clock.lap(0);
 
-  const auto t_kernel = std::chrono::steady_clock::now();
-  const uint8_t* const base = d_in.as<uint8_t>();
-  const double* const d_columns = reinterpret_cast<const double*>(base);
-  const double* const d_beams = reinterpret_cast<const double*>(base + column_bytes);
-  const double* const d_pose = reinterpret_cast<const double*>(base + column_bytes + beam_bytes);
-  const uint8_t* const d_packets = base + column_bytes + beam_bytes + pose_bytes;  // 8-byte aligned: the kernel's dword loads need 4
-  const dim3 grid(static_cast<unsigned>(C), static_cast<unsigned>(num_packets)), block(kOusterThreads);
-  if (profile == kOusterLegacy)
-    hipLaunchKernelGGL(k_ouster_decode<kOusterLegacy>, grid, block, 0, nullptr, d_packets, (long long)packet_stride, H, W, d_columns, d_beams, d_pose, (unsigned long long)ts0,
-                       d_rec.as<uint32_t>(), d_col.as<int32_t>());
-  else if (profile == kOusterRng19)
-    hipLaunchKernelGGL(k_ouster_decode<kOusterRng19>, grid, block, 0, nullptr, d_packets, (long long)packet_stride, H, W, d_columns, d_beams, d_pose, (unsigned long long)ts0,
-                       d_rec.as<uint32_t>(), d_col.as<int32_t>());
-  else
-    hipLaunchKernelGGL(k_ouster_decode<kOusterRng15>, grid, block, 0, nullptr, d_packets, (long long)packet_stride, H, W, d_columns, d_beams, d_pose, (unsigned long long)ts0,
-                       d_rec.as<uint32_t>(), d_col.as<int32_t>());
-  HIP_TRY(hipGetLastError());
-  if (returns_per_packet) {
-    hipLaunchKernelGGL(k_ouster_sum_returns, dim3(static_cast<unsigned>((num_packets + 63) / 64)), dim3(64), 0, nullptr, d_col.as<int32_t>(), int(num_packets), C, d_ret.as<int32_t>());
-    HIP_TRY(hipGetLastError());
-  }
+  hipError_t launched = hipErrorInvalidValue;
+  with_int<kOusterLegacy, kOusterRng19, kOusterRng15>(profile, [&](auto P) {
+    launched = launch(k_ouster_decode<P>, dim3(unsigned(C), unsigned(num_packets)), kOusterThreads, 0, nullptr, stage.device<uint8_t>(o_packets), packet_stride, H, W,
+                      stage.device<double>(o_columns), stage.device<double>(o_beams), stage.device<double>(o_pose), ts0, d_rec.as<uint32_t>(), d_col.as<int32_t>());
+  });
+  HIP_TRY(launched);
+  if (returns_per_packet) HIP_TRY(launch(k_ouster_sum_returns, blocks_for(num_packets, 64), 64, 0, nullptr, d_col.as<int32_t>(), int(num_packets), C, d_ret.as<int32_t>()));
   HIP_TRY(hipStreamSynchronize(nullptr));
-  g_ouster_ms[1] = ms_since(t_kernel);
+  g_ouster_clock.lap(1);
 
-  const auto t_copy = std::chrono::steady_clock::now();
   HIP_TRY(hipMemcpy(records_out, d_rec.as<void>(), record_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
   if (returns_per_packet) HIP_TRY(hipMemcpy(returns_per_packet, d_ret.as<void>(), N * sizeof(int32_t), hipMemcpyDeviceToHost));
-  g_ouster_ms[2] = ms_since(t_copy);
+  g_ouster_clock.lap(2);
   return NIDREG_OK;
 }
 
-int nidreg_ouster_get_timing(double* ms3) {
-  if (!ms3) return fail(NIDREG_ERR_INVALID, "nidreg_ouster_get_timing: null argument");
-  std::memcpy(ms3, g_ouster_ms, sizeof(g_ouster_ms));
-  return NIDREG_OK;
-}
+int nidreg_ouster_get_timing(double* ms3) { return g_ouster_clock.read("nidreg_ouster_get_timing", ms3); }
 
 }  // extern "C"

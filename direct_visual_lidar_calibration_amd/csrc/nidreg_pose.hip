@@ -88,20 +88,17 @@ namespace {
 
 hipError_t launch_ransac_score(int model, const double* d_corr, int n, int tile, int ntiles, const double* d_Rs, int iterations, const CamParams<double>& cam, double thresh_sq,
                                int* d_counts) {
-  const unsigned grid = unsigned((iterations + kPoseTileH - 1) / kPoseTileH) * unsigned(ntiles);
+  const unsigned grid = blocks_for(iterations, kPoseTileH) * unsigned(ntiles);
   const size_t lds = size_t(5) * size_t(tile) * sizeof(double);  // <= 40 KB
   return with_model(model, hipErrorInvalidValue, [&](auto M) {
-    hipLaunchKernelGGL((k_ransac_score<M>), dim3(grid), dim3(kPoseThreads), lds, nullptr, d_corr, n, tile, ntiles, d_Rs, iterations, cam, thresh_sq, d_counts);
-    return hipGetLastError();
+    return launch(k_ransac_score<M>, grid, kPoseThreads, lds, nullptr, d_corr, n, tile, ntiles, d_Rs, iterations, cam, thresh_sq, d_counts);
   });
 }
 
 hipError_t launch_ransac_flags(int model, const double* d_corr, int n, const double* d_Rs, const pose_u64* d_best, const CamParams<double>& cam, double thresh_sq,
                                unsigned char* d_flags, double* d_R_out) {
-  const unsigned grid = unsigned((n + kPoseThreads - 1) / kPoseThreads);
   return with_model(model, hipErrorInvalidValue, [&](auto M) {
-    hipLaunchKernelGGL((k_ransac_flags<M>), dim3(grid), dim3(kPoseThreads), 0, nullptr, d_corr, n, d_Rs, d_best, cam, thresh_sq, d_flags, d_R_out);
-    return hipGetLastError();
+    return launch(k_ransac_flags<M>, blocks_for(n, kPoseThreads), kPoseThreads, 0, nullptr, d_corr, n, d_Rs, d_best, cam, thresh_sq, d_flags, d_R_out);
   });
 }
 
@@ -188,12 +185,10 @@ int nidreg_estimate_rotation_ransac(int model_id, const double* intrinsics, cons
   const double* const d_corr = d_in.as<double>();
   const CamParams<double> cam = make_cam(model_id, intrinsics, distortion);
   const double thresh_sq = error_thresh * error_thresh;
-  const unsigned hgrid = unsigned((iterations + kPoseThreads - 1) / kPoseThreads);
-  hipLaunchKernelGGL(k_ransac_hypotheses, dim3(hgrid), dim3(kPoseThreads), 0, nullptr, d_corr + 5 * sn, d_corr + 8 * sn, N, iterations, pose_u64(seed), d_pairs_in.as<int>(), d_Rs.as<double>());
-  HIP_TRY(hipGetLastError());
+  const unsigned hgrid = blocks_for(iterations, kPoseThreads);
+  HIP_TRY(launch(k_ransac_hypotheses, hgrid, kPoseThreads, 0, nullptr, d_corr + 5 * sn, d_corr + 8 * sn, N, iterations, seed, d_pairs_in.as<int>(), d_Rs.as<double>()));
   HIP_TRY(launch_ransac_score(model_id, d_corr, N, tile, ntiles, d_Rs.as<double>(), iterations, cam, thresh_sq, d_counts));
-  hipLaunchKernelGGL(k_ransac_best, dim3(hgrid), dim3(kPoseThreads), 0, nullptr, d_counts, iterations, d_best);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch(k_ransac_best, hgrid, kPoseThreads, 0, nullptr, d_counts, iterations, d_best));
   HIP_TRY(launch_ransac_flags(model_id, d_corr, N, d_Rs.as<double>(), d_best, cam, thresh_sq, d_flags, d_R_out));
   std::vector<unsigned char> out(res_bytes);
   HIP_TRY(hipMemcpy(out.data(), d_res.as<void>(), res_bytes, hipMemcpyDeviceToHost));  // (synchronises the null stream)

@@ -1,12 +1,8 @@
 // nidreg_raw.hip -- C ABI of the raw image encodings (include/nidreg.h: nidreg_image_to_mono8) and the translation unit of their
 // kernels (nid_raw_kernels.hpp).  Stateless, like nidreg_draw: validation (all of it BEFORE the device is touched), upload of the
 // message's bytes as they lie, one launch, the copy back.  No CPU path for the arithmetic.
-#include "nid_launch.hpp"
+#include "nid_host.hpp"
 #include "nid_raw_kernels.hpp"
-
-#include <chrono>
-#include <cstring>
-#include <string>
 
 using namespace nidreg;
 
@@ -16,7 +12,7 @@ constexpr int kRawMaxDim = 16384;
 const char* const kRawList =
     "mono8, mono16, rgb8, bgr8, rgba8, bgra8, rgb16, bgr16, rgba16, bgra16, yuv422, uyvy, yuv422_yuy2, yuyv and bayer_{rggb,bggr,gbrg,grbg}{8,16} are";
 
-thread_local double g_raw_ms[3] = {0, 0, 0};  // of this thread's last nidreg_image_to_mono8: upload, kernel, copy back
+thread_local PhaseClock<3> g_raw_clock;  // of this thread's last nidreg_image_to_mono8: upload, kernel, copy back
 
 struct RawEncoding {
   const char* name;
@@ -34,8 +30,6 @@ const RawEncoding kRawEncodings[] = {
     {"bayer_bggr8", 1, 1, 0, 1, 1, 0}, {"bayer_gbrg8", 1, 1, 0, 0, 1, 0}, {"bayer_grbg8", 1, 1, 0, 1, 0, 0}, {"bayer_rggb16", 2, 1, 0, 0, 0, 0}, {"bayer_bggr16", 2, 1, 0, 1, 1, 0},
     {"bayer_gbrg16", 2, 1, 0, 0, 1, 0}, {"bayer_grbg16", 2, 1, 0, 1, 0, 0},
 };
-
-double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 
 }  // namespace
 
@@ -63,7 +57,7 @@ int nidreg_image_to_mono8(int device_id, const uint8_t* data, int64_t size, int 
   const int64_t stride = out_row_stride > 0 ? out_row_stride : int64_t(width);
   if (const int rc = use_device(who.c_str(), device_id)) return rc;
 
-  const auto t_upload = std::chrono::steady_clock::now();
+  g_raw_clock.start();
   const size_t W = size_t(width), H = size_t(height);
   const int w4 = (width + 3) / 4;
   const size_t dev_stride = size_t(w4) * 4;  // device image: rows of whole 4-byte groups
@@ -72,38 +66,27 @@ int nidreg_image_to_mono8(int device_id, const uint8_t* data, int64_t size, int 
   HIP_TRY(d_src.alloc(src_bytes));
   HIP_TRY(d_out.alloc(dev_stride * H));
   HIP_TRY(hipMemcpy(d_src.as<void>(), data, src_bytes, hipMemcpyHostToDevice));
-  g_raw_ms[0] = ms_since(t_upload);
+  g_raw_clock.lap(0);
 
-  const auto t_kernel = std::chrono::steady_clock::now();
-  const long long groups = (long long)w4 * height;
-  const dim3 grid(unsigned((groups + kRawThreads - 1) / kRawThreads)), block(kRawThreads);
+  const unsigned grid = blocks_for((long long)w4 * height, kRawThreads);
   const int big = e->sample_bytes == 2 && is_bigendian != 0;  // 8-bit encodings ignore the flag
-  if (e->channels == 0) {
-    if (e->sample_bytes == 1)
-      hipLaunchKernelGGL(k_raw_bayer<1>, grid, block, 0, nullptr, d_src.as<uint8_t>(), (long long)step, e->r, e->g, big, width, w4, height, d_out.as<uint8_t>(), (long long)dev_stride);
+  const RawFormat f = {pixel_bytes, e->channels, e->r * e->sample_bytes, e->g * e->sample_bytes, e->b * e->sample_bytes, big};
+  hipError_t launched = hipErrorInvalidValue;
+  with_int<1, 2>(e->sample_bytes, [&](auto BYTES) {
+    if (e->channels == 0)
+      launched = launch(k_raw_bayer<BYTES>, grid, kRawThreads, 0, nullptr, d_src.as<uint8_t>(), step, e->r, e->g, big, width, w4, height, d_out.as<uint8_t>(), dev_stride);
     else
-      hipLaunchKernelGGL(k_raw_bayer<2>, grid, block, 0, nullptr, d_src.as<uint8_t>(), (long long)step, e->r, e->g, big, width, w4, height, d_out.as<uint8_t>(), (long long)dev_stride);
-  } else {
-    const RawFormat f = {pixel_bytes, e->channels, e->r * e->sample_bytes, e->g * e->sample_bytes, e->b * e->sample_bytes, big};
-    if (e->sample_bytes == 1)
-      hipLaunchKernelGGL(k_raw_pixels<1>, grid, block, 0, nullptr, d_src.as<uint8_t>(), (long long)step, f, width, w4, height, d_out.as<uint8_t>(), (long long)dev_stride);
-    else
-      hipLaunchKernelGGL(k_raw_pixels<2>, grid, block, 0, nullptr, d_src.as<uint8_t>(), (long long)step, f, width, w4, height, d_out.as<uint8_t>(), (long long)dev_stride);
-  }
-  HIP_TRY(hipGetLastError());
+      launched = launch(k_raw_pixels<BYTES>, grid, kRawThreads, 0, nullptr, d_src.as<uint8_t>(), step, f, width, w4, height, d_out.as<uint8_t>(), dev_stride);
+  });
+  HIP_TRY(launched);
   HIP_TRY(hipStreamSynchronize(nullptr));
-  g_raw_ms[1] = ms_since(t_kernel);
+  g_raw_clock.lap(1);
 
-  const auto t_copy = std::chrono::steady_clock::now();
   HIP_TRY(hipMemcpy2D(out, size_t(stride), d_out.as<void>(), dev_stride, W, H, hipMemcpyDeviceToHost));  // W bytes a row: the caller's padding stays
-  g_raw_ms[2] = ms_since(t_copy);
+  g_raw_clock.lap(2);
   return NIDREG_OK;
 }
 
-int nidreg_image_get_timing(double* ms3) {
-  if (!ms3) return fail(NIDREG_ERR_INVALID, "nidreg_image_get_timing: null argument");
-  std::memcpy(ms3, g_raw_ms, sizeof(g_raw_ms));
-  return NIDREG_OK;
-}
+int nidreg_image_get_timing(double* ms3) { return g_raw_clock.read("nidreg_image_get_timing", ms3); }
 
 }  // extern "C"

@@ -23,14 +23,12 @@ bool size_ok(int width, int height) { return width >= 1 && width <= kMaskMaxDim 
 namespace nidreg {
 
 hipError_t launch_select_scan(const int* d_count, int ntiles, int* d_offset) {
-  hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(kSelectThreads), 0, nullptr, d_count, ntiles, d_offset);
-  return hipGetLastError();
+  return launch(k_select_scan, 1, kSelectThreads, 0, nullptr, d_count, ntiles, d_offset);
 }
 
 hipError_t launch_select_scatter(const unsigned char* d_flag, const int* d_offset, int ntiles, const double* d_pts, const double* d_int, long long n, int32_t* d_idx_out, double* d_pts_out,
                                  double* d_int_out) {
-  hipLaunchKernelGGL(k_select_scatter, dim3(unsigned(ntiles)), dim3(kSelectThreads), 0, nullptr, d_flag, d_offset, d_pts, d_int, n, d_idx_out, d_pts_out, d_int_out);
-  return hipGetLastError();
+  return launch(k_select_scatter, unsigned(ntiles), kSelectThreads, 0, nullptr, d_flag, d_offset, d_pts, d_int, n, d_idx_out, d_pts_out, d_int_out);
 }
 
 }  // namespace nidreg
@@ -58,11 +56,9 @@ int nidreg_mask_create(int device_id, const uint8_t* mask, int width, int height
     HIP_TRY(d_src.alloc(bytes));
     HIP_TRY(d_rows.alloc(bytes));
     HIP_TRY(hipMemcpy2D(d_src.as<void>(), size_t(width), mask, size_t(row_stride), size_t(width), size_t(height), hipMemcpyHostToDevice));
-    const unsigned grid = unsigned((bytes + 255) / 256);
-    hipLaunchKernelGGL(k_mask_erode, dim3(grid), dim3(256), 0, nullptr, d_src.as<uint8_t>(), d_rows.as<uint8_t>(), width, height, margin, 1);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_mask_erode, dim3(grid), dim3(256), 0, nullptr, d_rows.as<uint8_t>(), m->d_eroded.as<uint8_t>(), width, height, margin, 0);
-    HIP_TRY(hipGetLastError());
+    const unsigned grid = blocks_for(bytes, 256);
+    HIP_TRY(launch(k_mask_erode, grid, 256, 0, nullptr, d_src.as<uint8_t>(), d_rows.as<uint8_t>(), width, height, margin, 1));
+    HIP_TRY(launch(k_mask_erode, grid, 256, 0, nullptr, d_rows.as<uint8_t>(), m->d_eroded.as<uint8_t>(), width, height, margin, 0));
     HIP_TRY(hipStreamSynchronize(nullptr));  // the temporaries are freed on return
   }
   *out = m.release();
@@ -148,12 +144,9 @@ int nidreg_cloud_select(const nidreg_cloud* cloud, int model_id, const double* i
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_zbuf), 0x7f800000, size_t(width) * height, nullptr));
     HIP_TRY(launch_cull(model_id, intrinsics, distortion, cloud->d_pts.as<double>(), 4, n, T_camera_lidar, width, height, min_z, enable_depth_buffer_culling ? 1 : 0, d_pix,
                         d_zbuf, d_keep, nullptr));
-    hipLaunchKernelGGL(k_select_flags, dim3(unsigned(ntiles)), dim3(kSelectThreads), 0, nullptr, d_keep, d_pix,
-                       mask ? mask->d_eroded.as<uint8_t>() : static_cast<const uint8_t*>(nullptr), cloud->d_pts.as<double>(), (long long)n, min2, max2, d_flag,
-                       d_count);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(kSelectThreads), 0, nullptr, d_count, ntiles, d_offset);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(k_select_flags, unsigned(ntiles), kSelectThreads, 0, nullptr, d_keep, d_pix, mask ? mask->d_eroded.as<uint8_t>() : nullptr, cloud->d_pts.as<double>(), n, min2, max2,
+                   d_flag, d_count));
+    HIP_TRY(launch_select_scan(d_count, ntiles, d_offset));
     HIP_TRY(hipMemcpy(sums, d_offset + ntiles, sizeof(sums), hipMemcpyDeviceToHost));  // (synchronises the null stream)
     total = sums[0];
     if (total < 0 || int64_t(total) > n) return fail(NIDREG_ERR_HIP, std::string(who) + ": the scan counted " + std::to_string(total) + " of " + std::to_string(n) + " points");
@@ -161,9 +154,7 @@ int nidreg_cloud_select(const nidreg_cloud* cloud, int model_id, const double* i
     HIP_TRY(c->d_pts.alloc(m1 * 32));
     HIP_TRY(c->d_int.alloc(m1 * 8));
     if (total > 0) {
-      hipLaunchKernelGGL(k_select_scatter, dim3(unsigned(ntiles)), dim3(kSelectThreads), 0, nullptr, d_flag, d_offset, cloud->d_pts.as<double>(),
-                         cloud->d_int.as<double>(), (long long)n, d_idx, c->d_pts.as<double>(), c->d_int.as<double>());
-      HIP_TRY(hipGetLastError());
+      HIP_TRY(launch_select_scatter(d_flag, d_offset, ntiles, cloud->d_pts.as<double>(), cloud->d_int.as<double>(), n, d_idx, c->d_pts.as<double>(), c->d_int.as<double>()));
       if (indices_out) HIP_TRY(hipMemcpy(indices_out, d_idx, size_t(total) * sizeof(int32_t), hipMemcpyDeviceToHost));
       HIP_TRY(hipStreamSynchronize(nullptr));  // the scratch is freed on return
     }

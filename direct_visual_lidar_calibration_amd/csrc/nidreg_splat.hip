@@ -3,7 +3,7 @@
 // evaluation kernels' sources: nidreg_kernel_build() does not cover it.  Host side: device residency and launches.  No CPU path.
 #define NID_RENDER_FRONT_END_ONLY  // the non-template kernels of nid_render_kernels.hpp belong to nid_kernels_f64_exact.hip
 #include "nid_splat_kernels.hpp"
-#include "nid_launch.hpp"
+#include "nid_host.hpp"
 
 #include <memory>
 #include <string>
@@ -102,15 +102,12 @@ int nidreg_splat_draw(nidreg_splat* s, int model_id, const double* intrinsics, c
     const CamParams<double> cam = make_cam(model_id, intrinsics, distortion);
     IsoParams<double> iso;
     for (int k = 0; k < 12; k++) iso.m[k] = T_view_lidar[k];
-    const unsigned grid = unsigned((s->n + 255) / 256);
     HIP_TRY(with_model(model_id, hipErrorInvalidValue, [&](auto M) {
-      hipLaunchKernelGGL((k_splat_depth<M>), dim3(grid), dim3(256), 0, s->stream, s->d_pts.as<double>(), s->stride_d, s->n, iso, cam, width, height, min_nz, radius, s->d_zkey.as<u64>());
-      return hipGetLastError();
+      return launch(k_splat_depth<M>, blocks_for(s->n, 256), 256, 0, s->stream, s->d_pts.as<double>(), s->stride_d, s->n, iso, cam, width, height, min_nz, radius, s->d_zkey.as<u64>());
     }));
   }
-  hipLaunchKernelGGL(k_splat_resolve, dim3(unsigned((npix + 255) / 256)), dim3(256), 0, s->stream, s->d_zkey.as<u64>(), (long long)npix, s->d_rgba.as<uchar4>(),
-                     background_rgb ? s->d_bg.as<uint8_t>() : nullptr, alpha, s->d_rgb.as<uint8_t>(), out_index ? s->d_index.as<int>() : nullptr);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch(k_splat_resolve, blocks_for(npix, 256), 256, 0, s->stream, s->d_zkey.as<u64>(), npix, s->d_rgba.as<uchar4>(), background_rgb ? s->d_bg.as<uint8_t>() : nullptr, alpha,
+                 s->d_rgb.as<uint8_t>(), out_index ? s->d_index.as<int>() : nullptr));
   HIP_TRY(hipMemcpyAsync(out_rgb, s->d_rgb.as<void>(), npix * 3, hipMemcpyDeviceToHost, s->stream));
   if (out_index) HIP_TRY(hipMemcpyAsync(out_index, s->d_index.as<void>(), npix * sizeof(int), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));

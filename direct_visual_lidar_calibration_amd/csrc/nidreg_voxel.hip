@@ -9,7 +9,6 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -34,13 +33,14 @@ struct nidreg_integrator {
 };
 
 namespace nidreg {
+
+unsigned vox_grid(int64_t n) { return unsigned(std::max<int64_t>(1, std::min<int64_t>((n + kVoxThreads - 1) / kVoxThreads, kVoxMaxBlocks))); }
+
 namespace {
 
 constexpr int64_t kInitialCap = int64_t(1) << 16;  // 2 MB
 constexpr int64_t kMaxCap = int64_t(1) << 31;      // slot numbers are 32-bit (64 GB of table)
 constexpr int64_t kChunk = int64_t(1) << 20;       // points per claim / payload launch pair: bounds the slot scratch and how far the table is grown ahead
-
-unsigned vox_grid(int64_t n) { return unsigned(std::max<int64_t>(1, std::min<int64_t>((n + kVoxThreads - 1) / kVoxThreads, kVoxMaxBlocks))); }
 
 int64_t pow2_at_least(int64_t v) {
   int64_t c = kInitialCap;
@@ -57,8 +57,7 @@ int vox_reserve(nidreg_integrator* h, int64_t need) {
   HIP_TRY(fresh.alloc(size_t(cap) * sizeof(VoxSlot)));
   HIP_TRY(hipMemsetAsync(fresh.as<void>(), 0, size_t(cap) * sizeof(VoxSlot), nullptr));
   if (h->size > 0) {
-    hipLaunchKernelGGL(k_vox_rehash, dim3(vox_grid(h->cap)), dim3(kVoxThreads), 0, nullptr, h->d_slots.as<VoxSlot>(), (long long)h->cap, fresh.as<VoxSlot>(), unsigned(cap - 1));
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(k_vox_rehash, vox_grid(h->cap), kVoxThreads, 0, nullptr, h->d_slots.as<VoxSlot>(), h->cap, fresh.as<VoxSlot>(), unsigned(cap - 1)));
     HIP_TRY(hipStreamSynchronize(nullptr));  // the old table is freed below
   }
   h->d_slots = std::move(fresh);
@@ -80,8 +79,7 @@ template <typename Frame>
 int vox_insert(nidreg_integrator* h, const char* who, const Frame& frame, int64_t n, int64_t* num_skipped = nullptr) {
   vox_u64* const d_cnt = h->d_counters.as<vox_u64>();
   HIP_TRY(hipMemsetAsync(d_cnt + 1, 0, 3 * sizeof(vox_u64), nullptr));
-  hipLaunchKernelGGL((k_vox_check<Frame>), dim3(vox_grid(n)), dim3(kVoxThreads), 0, nullptr, frame, (long long)n, h->res, h->min_distance, d_cnt);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch(k_vox_check<Frame>, vox_grid(n), kVoxThreads, 0, nullptr, frame, n, h->res, h->min_distance, d_cnt));
   vox_u64 cnt[4];
   HIP_TRY(hipMemcpy(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost));
   if (num_skipped) {
@@ -115,12 +113,9 @@ int vox_insert(nidreg_integrator* h, const char* who, const Frame& frame, int64_
       if (const int rc = vox_reserve(h, size_bound + m)) return rc;
     }
     const vox_u64 seq0 = vox_u64(h->offered + i0);
-    hipLaunchKernelGGL((k_vox_claim<Frame>), dim3(vox_grid(m)), dim3(kVoxThreads), 0, nullptr, frame, (long long)i0, (long long)m, seq0, h->res, h->min_distance, h->d_slots.as<VoxSlot>(),
-                       unsigned(h->cap - 1), h->d_slot_of.as<unsigned>(), d_cnt);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL((k_vox_payload<Frame>), dim3(vox_grid(m)), dim3(kVoxThreads), 0, nullptr, frame, (long long)i0, (long long)m, seq0, h->d_slots.as<VoxSlot>(),
-                       h->d_slot_of.as<unsigned>());
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(k_vox_claim<Frame>, vox_grid(m), kVoxThreads, 0, nullptr, frame, i0, m, seq0, h->res, h->min_distance, h->d_slots.as<VoxSlot>(), unsigned(h->cap - 1),
+                   h->d_slot_of.as<unsigned>(), d_cnt));
+    HIP_TRY(launch(k_vox_payload<Frame>, vox_grid(m), kVoxThreads, 0, nullptr, frame, i0, m, seq0, h->d_slots.as<VoxSlot>(), h->d_slot_of.as<unsigned>()));
     size_bound += m;
   }
   if (const int rc = vox_read_size(h, &h->size)) return rc;
@@ -138,24 +133,15 @@ int vox_frame_room(nidreg_integrator* h, size_t bytes) {
 // sensor_msgs/PointField datatype -> bytes; 0 = not a type the route reads
 int cloud2_type_bytes(int32_t t) { return t == kPcUint8 ? 1 : t == kPcUint16 ? 2 : (t == kPcUint32 || t == kPcFloat32) ? 4 : t == kPcFloat64 ? 8 : 0; }
 
-template <int XyzType, int IntType>
-void cloud2_launch(const VoxCloud2& c, double4* pts, double* inten) {
-  const dim3 grid(vox_grid(c.n)), block(kVoxThreads);
-  if (c.step <= kVoxStageStep)
-    hipLaunchKernelGGL((k_vox_decode_cloud2<XyzType, IntType, true>), grid, block, 0, nullptr, c, pts, inten);
-  else
-    hipLaunchKernelGGL((k_vox_decode_cloud2<XyzType, IntType, false>), grid, block, 0, nullptr, c, pts, inten);
-}
-
-template <int XyzType>
-void cloud2_launch(const VoxCloud2& c, int32_t intensity_datatype, double4* pts, double* inten) {
-  switch (intensity_datatype) {
-    case kPcUint8: return cloud2_launch<XyzType, kPcUint8>(c, pts, inten);
-    case kPcUint16: return cloud2_launch<XyzType, kPcUint16>(c, pts, inten);
-    case kPcUint32: return cloud2_launch<XyzType, kPcUint32>(c, pts, inten);
-    case kPcFloat32: return cloud2_launch<XyzType, kPcFloat32>(c, pts, inten);
-    default: return cloud2_launch<XyzType, kPcFloat64>(c, pts, inten);
-  }
+// the decode kernel of the PointCloud2 route for the field types integrator_stage_cloud2 has accepted, staged or not by the step
+hipError_t cloud2_launch(const VoxCloud2& c, int32_t xyz_datatype, int32_t intensity_datatype, double4* pts, double* inten) {
+  hipError_t e = hipErrorInvalidValue;
+  with_int<kPcFloat32, kPcFloat64>(xyz_datatype, [&](auto X) {
+    with_field_type(intensity_datatype, [&](auto I) {
+      with_bool(c.step <= kVoxStageStep, [&](auto STAGED) { e = launch(k_vox_decode_cloud2<X, I, STAGED>, vox_grid(c.n), kVoxThreads, 0, nullptr, c, pts, inten); });
+    });
+  });
+  return e;
 }
 
 }  // namespace
@@ -286,18 +272,13 @@ int nidreg_integrator_insert_cloud2(nidreg_integrator* h, const void* data, int6
   double* d_int = nullptr;
   if (const int rc = integrator_stage_cloud2(h, who, data, num_points, point_step, x_offset, y_offset, z_offset, xyz_datatype, intensity_offset, intensity_datatype, &c, &d_pts, &d_int)) return rc;
   if (num_points == 0) return NIDREG_OK;
-  if (xyz_datatype == kPcFloat32)
-    cloud2_launch<kPcFloat32>(c, intensity_datatype, d_pts, d_int);
-  else
-    cloud2_launch<kPcFloat64>(c, intensity_datatype, d_pts, d_int);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(cloud2_launch(c, xyz_datatype, intensity_datatype, d_pts, d_int));
   return integrator_insert_staged(h, who, num_points, num_skipped);
 }
 
 // host wall-clock milliseconds of the calling thread's last nidreg_integrator_insert_las: checks + allocation + upload, decode kernel
 // (launch to idle), the integrator's passes
-static thread_local double g_las_ms[3] = {0.0, 0.0, 0.0};
-static double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+static thread_local PhaseClock<3> g_las_clock;
 
 // LAS point formats 0..10: the base record length, and where the red channel lies (0 = the format has no RGB)
 static const int kLasBaseLength[11] = {20, 28, 26, 34, 57, 63, 30, 36, 38, 59, 67};
@@ -307,8 +288,8 @@ int nidreg_integrator_insert_las(nidreg_integrator* h, const void* records, int6
                                  const double* origin3, int32_t intensity_source, const uint64_t* exclude_classes4, int32_t keep_withheld, int64_t* num_skipped) {
   const std::string who = "nidreg_integrator_insert_las";
   if (num_skipped) *num_skipped = 0;
-  g_las_ms[0] = g_las_ms[1] = g_las_ms[2] = 0.0;
-  auto t0 = std::chrono::steady_clock::now();
+  g_las_clock.clear();
+  g_las_clock.start();
   // every check of the arguments themselves comes before the handle is looked at, and all of it before the device is touched
   if (point_format < 0 || point_format > 10) return fail(NIDREG_ERR_INVALID, who + ": point formats 0..10 are read, got " + std::to_string(point_format));
   if (record_length < kLasBaseLength[point_format] || record_length > 65535)
@@ -329,8 +310,7 @@ int nidreg_integrator_insert_las(nidreg_integrator* h, const void* records, int6
   double* d_int = nullptr;
   if (const int rc = integrator_stage_cloud2(h, who.c_str(), records, num_points, record_length, 0, 4, 8, kPcFloat32, 12, kPcUint16, &c, &d_pts, &d_int)) return rc;
   if (num_points == 0) return NIDREG_OK;
-  g_las_ms[0] = ms_since(t0);
-  t0 = std::chrono::steady_clock::now();
+  g_las_clock.lap(0);
   const bool modern = point_format >= 6;
   VoxLas las;
   las.raw = c.raw, las.n = c.n, las.step = c.step;
@@ -344,25 +324,17 @@ int nidreg_integrator_insert_las(nidreg_integrator* h, const void* records, int6
   vox_u64 m[4] = {0, 0, 0, 0};
   if (exclude_classes4)
     for (int k = 0; k < 4; k++) m[k] = vox_u64(exclude_classes4[k]);
-  const dim3 grid(vox_grid(num_points)), block(kVoxThreads);
-  if (record_length <= kVoxStageStep)
-    hipLaunchKernelGGL((k_vox_decode_las<true>), grid, block, 0, nullptr, las, m[0], m[1], m[2], m[3], d_pts, d_int);
-  else
-    hipLaunchKernelGGL((k_vox_decode_las<false>), grid, block, 0, nullptr, las, m[0], m[1], m[2], m[3], d_pts, d_int);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(with_bool(record_length <= kVoxStageStep, [&](auto STAGED) {
+    return launch(k_vox_decode_las<STAGED>, vox_grid(num_points), kVoxThreads, 0, nullptr, las, m[0], m[1], m[2], m[3], d_pts, d_int);
+  }));
   HIP_TRY(hipStreamSynchronize(nullptr));  // (the check pass that follows reads its counters back, so the insert waits here anyway: this only splits the clock)
-  g_las_ms[1] = ms_since(t0);
-  t0 = std::chrono::steady_clock::now();
+  g_las_clock.lap(1);
   const int rc = integrator_insert_staged(h, who.c_str(), num_points, num_skipped);
-  g_las_ms[2] = ms_since(t0);
+  g_las_clock.lap(2);
   return rc;
 }
 
-int nidreg_integrator_las_timing(double* ms3) {
-  if (!ms3) return fail(NIDREG_ERR_INVALID, "nidreg_integrator_las_timing: null ms3");
-  for (int k = 0; k < 3; k++) ms3[k] = g_las_ms[k];
-  return NIDREG_OK;
-}
+int nidreg_integrator_las_timing(double* ms3) { return g_las_clock.read("nidreg_integrator_las_timing", ms3, "ms3"); }
 
 int nidreg_lzf_decompress(const uint8_t* in, int64_t in_size, uint8_t* out, int64_t out_size, int64_t* written) {
   if (written) *written = 0;
@@ -403,16 +375,14 @@ int nidreg_integrator_get(nidreg_integrator* h, float* records16, int64_t* seq) 
   HIP_TRY(d_out.alloc(sm * 24));  // m records, then m sequence numbers
   vox_u64* const cursor = h->d_counters.as<vox_u64>() + 3;
   HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(vox_u64), nullptr));
-  hipLaunchKernelGGL(k_vox_compact, dim3(vox_grid(h->cap)), dim3(kVoxThreads), 0, nullptr, h->d_slots.as<const VoxSlot>(), (long long)h->cap, cursor, d_keys.as<vox_u64>(), d_vals.as<unsigned>());
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch(k_vox_compact, vox_grid(h->cap), kVoxThreads, 0, nullptr, h->d_slots.as<const VoxSlot>(), h->cap, cursor, d_keys.as<vox_u64>(), d_vals.as<unsigned>()));
   size_t tmp_bytes = 0;
   HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_keys.as<vox_u64>(), d_keys2.as<vox_u64>(), d_vals.as<unsigned>(), d_vals2.as<unsigned>(), sm, 0, unsigned(end_bit), hipStream_t(nullptr)));
   HIP_TRY(d_tmp.alloc(std::max<size_t>(tmp_bytes, 1)));
   HIP_TRY(rocprim::radix_sort_pairs(d_tmp.as<void>(), tmp_bytes, d_keys.as<vox_u64>(), d_keys2.as<vox_u64>(), d_vals.as<unsigned>(), d_vals2.as<unsigned>(), sm, 0, unsigned(end_bit), hipStream_t(nullptr)));
   float4* const d_rec = d_out.as<float4>();
   long long* const d_seq = reinterpret_cast<long long*>(d_out.as<unsigned char>() + sm * 16);
-  hipLaunchKernelGGL(k_vox_gather, dim3(vox_grid(m)), dim3(kVoxThreads), 0, nullptr, h->d_slots.as<const VoxSlot>(), d_keys2.as<const vox_u64>(), d_vals2.as<const unsigned>(), (long long)m, d_rec, d_seq);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch(k_vox_gather, vox_grid(m), kVoxThreads, 0, nullptr, h->d_slots.as<const VoxSlot>(), d_keys2.as<const vox_u64>(), d_vals2.as<const unsigned>(), m, d_rec, d_seq));
   HIP_TRY(hipMemcpy(records16, d_rec, sm * 16, hipMemcpyDeviceToHost));
   if (seq) HIP_TRY(hipMemcpy(seq, d_seq, sm * 8, hipMemcpyDeviceToHost));
   return NIDREG_OK;

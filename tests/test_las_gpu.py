@@ -283,3 +283,25 @@ def test_preprocess_map_of_a_compressed_pcd_equals_the_binary_pcd(scene_files):
         assert files_b[name] == files_c[name], name
     assert calib_b["meta"].pop("data_path") == binary and calib_c["meta"].pop("data_path") == compressed
     assert calib_b == calib_c and "map_origin" not in calib_b["meta"]
+
+
+def test_the_phase_clock_is_read_cleared_by_a_refused_call_and_refused():
+    import ctypes
+    import math
+
+    from direct_visual_lidar_calibration_amd import _lib
+
+    lib = _lib.load()
+    rec = make_records(0, 1)
+    assert rec.shape == (1, 20)
+    a = preprocess.StaticPointCloudIntegrator(RES, 0.0)
+    try:
+        assert a.insert_las(rec.reshape(-1), 20, 0, SCALE, OFFSET, ORIGIN) == 0
+        ms = (ctypes.c_double * 3)(-1.0, -1.0, -1.0)
+        assert lib.nidreg_integrator_las_timing(ms) == 0 and all(math.isfinite(v) and v >= 0.0 for v in ms)  # upload, decode kernel, the integrator's passes
+        with pytest.raises(ValueError, match="point formats 0..10 are read, got 11"):
+            a.insert_las(rec.reshape(-1), 20, 11, SCALE, OFFSET, ORIGIN)
+        assert lib.nidreg_integrator_las_timing(ms) == 0 and list(ms) == [0.0, 0.0, 0.0]  # the call clears its clock before it checks anything
+        assert lib.nidreg_integrator_las_timing(None) == _lib.NIDREG_ERR_INVALID
+    finally:
+        a.close()

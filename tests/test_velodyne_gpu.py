@@ -154,3 +154,20 @@ def test_records_are_where_the_packet_bytes_are():
     xy, z = 10.0 * math.cos(math.radians(1.0)) + 0.0007 * math.sin(math.radians(1.0)), 10.0 * math.sin(math.radians(1.0)) - 0.0007 * math.cos(math.radians(1.0))
     assert np.abs(rec[hit[0], :3].astype(np.float64) - [0.0, -xy, z]).max() < 1e-5 and rec[hit[0], 3] == 200.0
     assert rec[hit[0], 4] == np.float32(0.25 + (19 * 55.296e-6 + 1 * 2.304e-6))
+
+
+def test_the_phase_clock_is_read_refused_and_kept_over_a_refused_call():
+    import ctypes
+
+    from direct_visual_lidar_calibration_amd import _lib
+
+    lib, model = _lib.load(), _model("vlp16")
+    _, view = vo.place_packets(_random_packets(1, 5), 1206, 0)
+    assert lidar_messages.velodyne_decode(view, 1, 1206, [0.0], model).shape == (384, 5)
+    ms = (ctypes.c_double * 3)(-1.0, -1.0, -1.0)
+    assert lib.nidreg_velodyne_get_timing(ms) == 0 and all(math.isfinite(v) and v >= 0.0 for v in ms)  # upload, kernel, copy back
+    assert lib.nidreg_velodyne_get_timing(None) == _lib.NIDREG_ERR_INVALID and _lib.last_error() == "nidreg_velodyne_get_timing: null argument"
+    with pytest.raises(ValueError, match="num_lasers 17"):
+        lidar_messages.velodyne_decode(view, 1, 1206, [0.0], model._replace(table=np.zeros((17, 8))))
+    after = (ctypes.c_double * 3)(-1.0, -1.0, -1.0)
+    assert lib.nidreg_velodyne_get_timing(after) == 0 and list(after) == list(ms)  # a refused call leaves the last call's values
